@@ -9,7 +9,12 @@ One timed *step* = one vectorised training iteration of ATT/main:248-447 on ever
 value = E_total * N * steps / max-over-ranks wall time.  Inputs are synthetic (seeded map, OD
 bank, random-init networks); the replay is pre-filled to 1e5 transitions before timing.
 
-python bench.py [--gpus N] [--steps K] [--warmup W]
+python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps, writes the last timed step's outputs when
+``--dump-outputs DIR`` is given (``dump_outputs``) and prints the result line.  ``--full`` adds every
+other measurement to that line: the CPU baselines, the env kernel's launch time and rooflines (10
+eager steps after the timed region), the grouped-GEMM and attention rooflines, the env-only
+microbenchmark, the world > 1 update schedule's overhead and the exact fix-up list's capacity check.
 N > 1: one process per GPU under torch.distributed.run (RCCL).  When WORLD_SIZE is already set (the
 driver's ``torch.distributed.run ... bench.py --gpus N``) this process is one rank; otherwise this
 process starts the N ranks itself as a child ``torch.distributed.run`` (before touching the GPU),
@@ -184,6 +189,13 @@ def parse():
                         "uam: config 5 (16 aircraft x 8192 envs, B=512)")
     p.add_argument("--steps", type=int, default=50)
     p.add_argument("--warmup", type=int, default=10)
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beyond the headline figure: CPU baselines, env launch timing and "
+                        "rooflines, GEMM / attention rooflines, env microbenchmark, world > 1 schedule overhead, "
+                        "fix-up list capacity check (each still has its own switch below)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed step computed (observation, reward and "
+                        "termination rows, learner parameters) as DIR/<name>.npy")
     p.add_argument("--envs", type=int, default=None, help="envs per GPU (default 4096; uam 8192)")
     p.add_argument("--agents", type=int, default=None, help="default 5 (att) / 8 (gru)")
     p.add_argument("--batch", type=int, default=None, help="default 1024 (att) / 512 (gru)")
@@ -607,6 +619,39 @@ def uam_env_microbench(E, N, iters=10):
             "achieved_GBs": gbs, "frac": gbs / HBM_PEAK_GBS}
 
 
+DUMP_BUDGET = 60 << 20      # bytes of .npy payload per --dump-outputs directory (under 64 MB with headers)
+
+
+def dump_outputs(tr, path):
+    """What the last timed step left with its caller, as ``path/<name>.npy``: the step's output
+    buffers (``tr.cur`` after the step: next observation rows after the auto-reset, reward, done,
+    mask, env_done, ...) as ``env_<field>`` and the learner's parameters after the step's update
+    (online and target networks) as ``learner_<name>``.  float64 stays float64, everything else is
+    written as float32.  When the env rows would pass DUMP_BUDGET, a fixed seeded sample of envs
+    (the same for every run at this size, ascending) is written instead of all of them."""
+    os.makedirs(path, exist_ok=True)
+
+    def host(t):
+        t = t.detach()
+        return t.cpu().numpy() if t.dtype == torch.float64 else t.to(torch.float32).cpu().numpy()
+
+    # the four networks of every learner (their parameters view the flat buffers the kernels update)
+    learner = {n: torch.cat([p.detach().reshape(-1) for p in getattr(tr.model, n).parameters()])
+               for n in ("actors", "critics", "actors_target", "critics_target")}
+    env = {k: v for k, v in vars(tr.cur).items() if torch.is_tensor(v)}
+    itemsize = lambda t: 8 if t.dtype == torch.float64 else 4     # noqa: E731
+    left = DUMP_BUDGET - sum(t.numel() * itemsize(t) for t in learner.values())
+    per_env = sum(t.numel() // tr.E * itemsize(t) for t in env.values())
+    keep = max(1, min(tr.E, left // per_env))
+    idx = None
+    if keep < tr.E:
+        idx = torch.from_numpy(np.sort(np.random.default_rng(20260).choice(tr.E, keep, replace=False)))
+    for k, t in env.items():
+        np.save(os.path.join(path, f"env_{k}.npy"), host(t if idx is None else t.index_select(0, idx.to(t.device))))
+    for k, t in learner.items():
+        np.save(os.path.join(path, f"learner_{k}.npy"), host(t))
+
+
 def main():
     a = parse()
     _trainer.NO_GRAPH = a.no_graph
@@ -625,7 +670,7 @@ def main():
             dist.destroy_process_group()
         return
     cpu = None
-    if ws0 == 1 and not a.no_cpu_baseline:
+    if a.full and ws0 == 1 and not a.no_cpu_baseline:
         # before any GPU initialisation: the pool's children must not inherit a GPU context
         cpu = cpu_baseline(a.envs, a.agents, a.batch, a.radar, a.cpu_seconds, model=a.model, procs_req=a.cpu_procs)
     ws, rank, local = setup_dist(a.backend)
@@ -679,50 +724,14 @@ def main():
     if ws > 1:
         dist.all_reduce(dt_t, op=dist.ReduceOp.MAX)
     dt = float(dt_t)
-    if graphed:
-        # the env launch is inside the step graphs: time it on 10 eager steps after the timed region
-        for k in range(10):
-            tr.step(update=True, time_env=True)
-        torch.cuda.synchronize()
-    env_ms = float(np.mean([e0.elapsed_time(e1) for e0, e1 in tr.env_events]))
-    # the exact threshold fix-up list never overflowed in this run (else the surplus rays kept their float
-    # decisions): checked once, after the timed region (synchronises)
-    band = None if a.model == "uam" else tr.env.check_band_capacity()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(tr, a.dump_outputs)      # the state the last timed step left, before any further step
     E_total = a.envs * ws
     N = a.agents
     value = E_total * N * a.steps / dt
     upd_per_s = a.steps / dt
     uam = a.model == "uam"
     D0 = 6 + 4 * (N - 1)
-    if uam:
-        bpa = uam_bytes_per_agent_step(N)
-    elif tr.gru:
-        bpa = env_bytes_per_agent_step(N, "wgru", float(np.mean(tr.bank.cnt)))
-    else:
-        bpa = env_bytes_per_agent_step(N)
-    push_bpa = 0.0
-    if not uam and tr.fused_tail:
-        # the fused tail's replay push: every ring row is written once; the fields this step produces
-        # (reward, done, next own / radar / nei) go to the ring from the kernel's registers / LDS, so
-        # only the carried-in fields (current obs rows, actions, hidden states) are read
-        push_bpa = 4.0 * (tr.replay.row_width + push_read_floats(tr.replay)) / N
-        bpa += push_bpa
-    achieved = bpa * a.envs * N / (env_ms * 1e-3) / 1e9
-    traffic = None
-    tsrc = None
-    tpath = os.path.join(ROOT, "profiles", "uam_env_pmc.json") if uam else a.traffic
-    if not uam and tpath and N != 5:     # per-N env PMC files (config 4: env_step_pmc_n8.json)
-        tpath = tpath.replace(".json", f"_n{N}.json")
-    if tpath and os.path.exists(tpath):
-        with open(tpath) as f:
-            t = json.load(f)
-        if t.get("envs") == a.envs and t.get("agents") == N and (
-                bool(t.get("tdcpa")) if uam else (t.get("variant", "att") == ("wgru" if tr.gru else "att") and
-                                                  t.get("radar") == ("obstacles" if tr.gru else a.radar) and
-                                                  t.get("maps", 1) == a.maps and
-                                                  bool(t.get("tail", False)) == tr.fused_tail)):
-            traffic = t.get("hbm_bytes_per_launch")
-            tsrc = os.path.relpath(tpath, ROOT)
     if uam:
         upd_fl = uam_update_flops(a.batch)
         workload = (f"tdCPA_forV2_changeskin_UAM: {N} aircraft x {a.envs} envs/GPU, drifting cloud + go-around "
@@ -758,19 +767,73 @@ def main():
                    "graph_segments": "one per update" if (ws == 1 or parallel.capturable(pg)) else
                    "cut at each gradient all-reduce"},
         "updates_per_s": upd_per_s, "grad_iters_per_s": upd_per_s * (1 if (tr.gru or uam) else N),
-        "env_roofline": {"kernel": "uam_step_kernel (fused UAM env step)" if uam else (
-                             "step_kernel (env step + replay push + auto-reset, aac_env_step_tail)" if tr.fused_tail
-                             else "step_kernel (fused env step)"),
-                         "push_bytes_per_agent_step": push_bpa,
-                         "bound": "hbm", "achieved": achieved,
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "traffic_source": tsrc, "bytes_per_agent_step": bpa, "agents_per_launch": a.envs * N,
-                         "avg_launch_ms": env_ms,
-                         "exact_band_list": None if band is None else {"most_per_launch": band[0], "capacity": band[1]}},
         "update_roofline": {"bound": "mfma", "unit": "TFLOP/s", "flop_per_update": upd_fl,
                             "achieved": upd_fl * upd_per_s / 1e12, "peak": peak,
                             "frac": upd_fl * upd_per_s / 1e12 / peak, "note": "whole-step rate bound"},
     }
+    if a.full:
+        full_measurements(a, tr, out, ws, rank, graphed, cpu)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if ws > 1:
+        dist.destroy_process_group()
+
+
+def full_measurements(a, tr, out, ws, rank, graphed, cpu):
+    """``--full``: everything the result line carries beyond the headline figure, measured after the
+    timed region (and after --dump-outputs): the env launch time and its rooflines, the exact fix-up
+    list's capacity check, the grouped-GEMM / attention rooflines, the env-only microbenchmark and the
+    world > 1 schedule's overhead; ``cpu`` is the CPU baseline taken before GPU initialisation."""
+    N = a.agents
+    uam = a.model == "uam"
+    if graphed:
+        # the env launch is inside the step graphs: time it on 10 eager steps after the timed region
+        for k in range(10):
+            tr.step(update=True, time_env=True)
+        torch.cuda.synchronize()
+    env_ms = float(np.mean([e0.elapsed_time(e1) for e0, e1 in tr.env_events]))
+    # the exact threshold fix-up list never overflowed in this run (else the surplus rays kept their float
+    # decisions): checked once, after the timed region (synchronises)
+    band = None if uam else tr.env.check_band_capacity()
+    if uam:
+        bpa = uam_bytes_per_agent_step(N)
+    elif tr.gru:
+        bpa = env_bytes_per_agent_step(N, "wgru", float(np.mean(tr.bank.cnt)))
+    else:
+        bpa = env_bytes_per_agent_step(N)
+    push_bpa = 0.0
+    if not uam and tr.fused_tail:
+        # the fused tail's replay push: every ring row is written once; the fields this step produces
+        # (reward, done, next own / radar / nei) go to the ring from the kernel's registers / LDS, so
+        # only the carried-in fields (current obs rows, actions, hidden states) are read
+        push_bpa = 4.0 * (tr.replay.row_width + push_read_floats(tr.replay)) / N
+        bpa += push_bpa
+    achieved = bpa * a.envs * N / (env_ms * 1e-3) / 1e9
+    traffic = None
+    tsrc = None
+    tpath = os.path.join(ROOT, "profiles", "uam_env_pmc.json") if uam else a.traffic
+    if not uam and tpath and N != 5:     # per-N env PMC files (config 4: env_step_pmc_n8.json)
+        tpath = tpath.replace(".json", f"_n{N}.json")
+    if tpath and os.path.exists(tpath):
+        with open(tpath) as f:
+            t = json.load(f)
+        if t.get("envs") == a.envs and t.get("agents") == N and (
+                bool(t.get("tdcpa")) if uam else (t.get("variant", "att") == ("wgru" if tr.gru else "att") and
+                                                  t.get("radar") == ("obstacles" if tr.gru else a.radar) and
+                                                  t.get("maps", 1) == a.maps and
+                                                  bool(t.get("tail", False)) == tr.fused_tail)):
+            traffic = t.get("hbm_bytes_per_launch")
+            tsrc = os.path.relpath(tpath, ROOT)
+    out["env_roofline"] = {"kernel": "uam_step_kernel (fused UAM env step)" if uam else (
+                               "step_kernel (env step + replay push + auto-reset, aac_env_step_tail)" if tr.fused_tail
+                               else "step_kernel (fused env step)"),
+                           "push_bytes_per_agent_step": push_bpa,
+                           "bound": "hbm", "achieved": achieved,
+                           "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                           "traffic_source": tsrc, "bytes_per_agent_step": bpa, "agents_per_launch": a.envs * N,
+                           "avg_launch_ms": env_ms,
+                           "exact_band_list": None if band is None else {"most_per_launch": band[0],
+                                                                         "capacity": band[1]}}
     if not uam and not tr.gru:
         # the env kernel's second roofline: fp64 arithmetic (SURVEY.md section 8(d) FLOP count), with
         # the fp64 VALU instruction counts of a PMC pass at this size when one is committed
@@ -819,10 +882,6 @@ def main():
         out["segmented_overhead_us"] = out["world_schedule"].get("segmented_overhead_us")
     if rank == 0 and cpu is not None:
         out["cpu_baseline"] = cpu
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if ws > 1:
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -8,12 +8,12 @@
 # --pmc pass is its own run with no trace domains.  Summaries: tools/evidence_summary.py.
 export TMPDIR=/tmp
 T="rocprofv3 --kernel-trace --output-format csv"
-SHORT="--steps 10 --warmup 3 --no-cpu-baseline --env-micro 0 --no-seg-overhead"
+SHORT="--full --steps 10 --warmup 3 --no-cpu-baseline --env-micro 0 --no-seg-overhead"
 if [ "$1" = bench ]; then
   bash tools/gpu_job.sh \
-    "bench:::300:::python bench.py" \
-    "bench_gru:::300:::python bench.py --model gru" \
-    "bench_uam:::300:::python bench.py --model uam" \
+    "bench:::300:::python bench.py --full" \
+    "bench_gru:::300:::python bench.py --full --model gru" \
+    "bench_uam:::300:::python bench.py --full --model uam" \
     "prof3:::240:::$T --stats -d gpurun_out/prof3 -o run -- python3 bench.py $SHORT" \
     "prof4:::240:::$T --stats -d gpurun_out/prof4 -o run -- python3 bench.py --model gru $SHORT" \
     "prof5:::240:::$T --stats -d gpurun_out/prof5 -o run -- python3 bench.py --model uam $SHORT"

@@ -1,6 +1,6 @@
 """Per-step kernel time of the last K steps of a rocprofv3 kernel trace, steps delimited by a
 marker kernel (default the env step kernel): python tools/trace_window.py run_kernel_trace.csv
-[K] [marker] [skip].  skip: trailing steps left out -- bench.py runs 10 eager env-timing steps after
+[K] [marker] [skip].  skip: trailing steps left out -- bench.py --full runs 10 eager env-timing steps after
 a graph-replayed timed region, so the timed steps of configs 3 and 4 are the ones before those."""
 import collections
 import csv

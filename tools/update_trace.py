@@ -1,5 +1,5 @@
 """Per-launch durations of one training step from a rocprofv3 kernel trace, between two
-replay-sample launches: python tools/update_trace.py run_kernel_trace.csv [which].  bench.py ends
+replay-sample launches: python tools/update_trace.py run_kernel_trace.csv [which].  bench.py --full ends
 with 4 eager updates for the GEMM roofline (CPU launch gaps), so the default window (-6) is the
 last graph-replayed step of the timed region."""
 import csv
