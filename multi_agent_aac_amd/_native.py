@@ -19,6 +19,7 @@ EXPORTS = (
     "aac_env_create", "aac_env_destroy", "aac_last_error", "aac_env_reset", "aac_env_step", "aac_env_step_tail",
     "aac_env_set_od_bank", "aac_env_set_od_banks", "aac_env_auto_reset", "aac_env_set_reset_compact", "aac_env_use_episode_buffer", "aac_env_get_state", "aac_env_set_state",
     "aac_env_band_max", "aac_astar", "aac_od_bank_build",
+    "aac_stats_last_error", "aac_stats_accumulate", "aac_stats_reduce",
 )
 
 vp = ctypes.c_void_p
@@ -44,6 +45,17 @@ class StepTail(ctypes.Structure):
                 ("size", ctypes.c_int64), ("meta", vp), ("n_fields", i32), ("srcs", ctypes.POINTER(vp)),
                 ("widths", ctypes.POINTER(i32)), ("dtypes", ctypes.POINTER(i32)), ("zero_rows", vp),
                 ("zero_width", i32), ("auto_reset", i32), ("pos_in", vp), ("pos_out", vp)]
+
+
+class StatsState(ctypes.Structure):        # aac_stats_state (include/aac_stats.h)
+    _fields_ = [("run_return", vp), ("run_len", vp), ("run_reach", vp), ("ep_count", vp), ("slots", vp),
+                ("log", vp), ("log_len", i32), ("log_meta", vp), ("fin_flag", vp), ("fin_row", vp), ("fin_list", vp)]
+
+
+class StatsStep(ctypes.Structure):         # aac_stats_step
+    _fields_ = [("reward", vp), ("reward_f64", i32), ("done", vp), ("mask", vp), ("env_done", vp), ("bbc", vp),
+                ("E", i32), ("N", i32), ("episode_length", i32), ("goal_bit", i32), ("return_mode", i32),
+                ("quota", vp), ("step_index", ctypes.c_int64)]
 
 
 _lib = None
@@ -76,6 +88,10 @@ def lib():
     L.aac_env_set_state.argtypes = [vp] + [vp] * 13 + [vp]
     L.aac_astar.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, i32]
     L.aac_od_bank_build.argtypes = [vp, i32, i32, vp, ctypes.c_double, i32, ctypes.c_uint64, i32, vp, vp, vp]
+    if hasattr(L, "aac_stats_accumulate") or not os.environ.get("AAC_LIB"):
+        L.aac_stats_last_error.restype = ctypes.c_char_p
+        L.aac_stats_accumulate.argtypes = [ctypes.POINTER(StatsState), ctypes.POINTER(StatsStep), vp]
+        L.aac_stats_reduce.argtypes = [ctypes.POINTER(StatsState), i32, vp, i32, vp]
     for name in EXPORTS:
         if os.environ.get("AAC_LIB") and not hasattr(L, name):
             continue          # an A/B experiment build of an earlier revision

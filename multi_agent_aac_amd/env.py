@@ -236,8 +236,8 @@ class BatchedEnv:
 
     def check_band_capacity(self):
         """Raise if any launch flagged more threshold-band rays (or variant-1 rewards) than the fix-up
-        list holds: the surplus would have kept their float decisions.  Synchronises; the trainers call
-        it once at the end of a run."""
+        list holds: the surplus would have kept their float decisions.  Synchronises; ``Trainer.finish()``
+        calls it once at the end of a run."""
         most, cap = self.band_max()
         if most > cap:
             raise RuntimeError(f"exact threshold fix-up list overflowed: {most} entries in one launch, capacity {cap}")

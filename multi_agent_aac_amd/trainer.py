@@ -71,6 +71,8 @@ class CheckpointMixin:
         extra = {f"cur.{k}": v for k, v in vars(self.cur).items() if torch.is_tensor(v)}
         if getattr(self, "gru", False):
             extra["h"] = self.h
+        if getattr(self, "stats", None) is not None:
+            extra.update({f"stats.{k}": v for k, v in self.stats.tensors().items()})
         return dict(learner=self.model, replay=self.replay, env=self.env, extra=extra)
 
     def save_checkpoint(self, path):
@@ -88,12 +90,33 @@ class CheckpointMixin:
                 self._sg, self._sg2 = {}, {}
             self._pos_dirty = True
 
+    def _init_stats(self, stats):
+        self.stats = None
+        if stats:
+            from .stats import EpisodeStats
+            self.stats = EpisodeStats.for_env(self.env)
+
+    def finish(self):
+        """End of a run: checks that no launch overflowed the env's exact threshold fix-up list
+        (``env.check_band_capacity``, where the env has one) and returns the episode statistics
+        (``stats.read()``; None without ``stats=True``).  Synchronises."""
+        if hasattr(self.env, "check_band_capacity"):
+            self.env.check_band_capacity()
+        return self.stats.read() if self.stats is not None else None
+
 
 class Trainer(CheckpointMixin):
     """Vectorised ATT/main loop (configs 2-3) or WGRU/ma_main loop (``model="gru"``, config 4) on one
-    GPU: E envs x N agents, B-row updates from a device replay of ``memory`` rows."""
+    GPU: E envs x N agents, B-row updates from a device replay of ``memory`` rows.
 
-    def __init__(self, E, N, B, memory, radar, seed, pg=None, model="att", maps=1):
+    ``stats=True`` keeps the reference's per-episode tallies (ATT/main:563-637) on the device in
+    ``self.stats`` (``stats.EpisodeStats``): one small launch after every env step, eager or inside
+    the whole-step graphs; ``finish()`` returns them.  Off (the default) the launch sequence is
+    unchanged and ``self.stats`` is None.  A checkpoint of a stats-enabled trainer carries the tallies
+    (``stats.*`` tensors) and resumes them exactly; loading a file saved without them into a
+    stats-enabled trainer raises a KeyError naming the missing tensor and changes nothing."""
+
+    def __init__(self, E, N, B, memory, radar, seed, pg=None, model="att", maps=1, stats=False):
         from . import world
         from .env import BatchedEnv
         from .maddpg import MADDPG
@@ -140,6 +163,7 @@ class Trainer(CheckpointMixin):
         # the auto-reset of an unfused tail and before the update).  A step with hooks runs eagerly
         # (no whole-step graph).  tests/oracle_diff.py hooks the C oracle in this way.
         self.pre_step_hooks, self.post_step_hooks = [], []
+        self._init_stats(stats)
 
     def graph_ok(self):
         """Whole-step graphs: the fused env tail, one rank, the fused learner (ATT: AAC_STEP_GRAPH; the
@@ -165,11 +189,15 @@ class Trainer(CheckpointMixin):
             srcs = [c.own, c.radar, c.nei, act, n.reward, n.done, n.own, n.radar, n.nei, hin, hn]
             self.env.step_tail(act, out=n, replay=self.replay, srcs=srcs, zero_rows=hn,
                                pos_io=(self.pos_dev[p], self.pos_dev[1 - p]))
+            if self.stats is not None:
+                self.stats.accumulate(n)
             self.model._plan(self.B).run()
             return
         act = self.model.act(c.own, c.radar, c.nei, self.episode, noisy=True)
         srcs = [c.own, c.radar, c.nei, act, n.reward, n.done, n.own, n.radar, n.nei]
         self.env.step_tail(act, out=n, replay=self.replay, srcs=srcs, pos_io=(self.pos_dev[p], self.pos_dev[1 - p]))
+        if self.stats is not None:
+            self.stats.accumulate(n)
         self.model._fused_plan(self.B).run_streams(side)
 
     def _capture_step(self, p, steps=1):
@@ -275,6 +303,8 @@ class Trainer(CheckpointMixin):
                 else:
                     srcs = [c.own, c.radar, c.nei, act, n.reward, n.done, n.own, n.radar, n.nei]
                     self.env.step_tail(act, out=n, replay=self.replay, srcs=srcs)
+                if self.stats is not None:
+                    self.stats.accumulate(n)
             if time_env:
                 ev1.record()
                 self.env_events.append((ev0, ev1))
@@ -287,6 +317,8 @@ class Trainer(CheckpointMixin):
             return
         with trace.range("env_step"):
             self.env.step(act, out=n)
+            if self.stats is not None:
+                self.stats.accumulate(n)
         if time_env:
             ev1.record()
             self.env_events.append((ev0, ev1))
@@ -343,9 +375,11 @@ def join_side(tr):
 
 class UamTrainer(CheckpointMixin):
     """Vectorised UAM/main:361-640 loop on one GPU: actor + noise, env step, one replay row per
-    aircraft, GPU auto-reset from the episode bank, one update_myown (one gradient iteration)."""
+    aircraft, GPU auto-reset from the episode bank, one update_myown (one gradient iteration).
+    ``stats=True``: episode tallies in ``self.stats``, checkpointed and returned by ``finish()`` as
+    ``Trainer``'s (a file saved without them raises a KeyError naming the tensor on load)."""
 
-    def __init__(self, E, N, B, memory, seed, pg=None):
+    def __init__(self, E, N, B, memory, seed, pg=None, stats=False):
         from . import uam, uam_learner
         self.E, self.N, self.B = E, N, B
         self.gru = False
@@ -367,6 +401,7 @@ class UamTrainer(CheckpointMixin):
         self._sg, self._sg2 = {}, {}                  # parity -> captured whole-step graph (1 / 2 steps)
         self.pos_dev = torch.zeros(2, dtype=torch.int64, device="cuda")   # ring position ping-pong
         self._pos_dirty = True
+        self._init_stats(stats)
 
     def graph_ok(self):
         """Whole-step graphs: one rank, the fused learner, the replay past one batch, no hooks."""
@@ -384,6 +419,8 @@ class UamTrainer(CheckpointMixin):
         c, n = self.bufs[p], self.bufs[1 - p]
         act = self.model.act(c.own, c.radar, self.episode, noisy=True)
         self.env.step(act, out=n)
+        if self.stats is not None:
+            self.stats.accumulate(n)
         self.replay.push_batch(c.own, c.radar, act, n.reward, n.done, n.own, n.radar,
                                pos_io=(self.pos_dev[p], self.pos_dev[1 - p]))
         fu = self.model.fused(self.B, self.replay)
@@ -465,6 +502,8 @@ class UamTrainer(CheckpointMixin):
             ev0.record()
         with trace.range("env_step"):
             self.env.step(act, out=n)
+            if self.stats is not None:
+                self.stats.accumulate(n)
         if time_env:
             ev1.record()
             self.env_events.append((ev0, ev1))
