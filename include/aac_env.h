@@ -26,6 +26,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "aac_record.h"
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -147,6 +149,13 @@ int aac_env_reset_stamps(unsigned long long *out, int32_t n_wg);
  * keeps it alive while the handle exists.  A trainer's noise schedule can read it directly.  The copy
  * is enqueued on `stream` (ordered after the caller's pending resets and its fill of the buffer). */
 int aac_env_use_episode_buffer(aac_env *env, int32_t *episode_dev, void *stream);
+
+/* Flight recorder (aac_record.h): aac_record with E and the state sources of ``step`` (pos, vel, goal,
+ * map_idx and the episode counter, wherever aac_env_use_episode_buffer has put it) filled from the
+ * handle's live device pointers at call time; the rest of ``step`` is the caller's.  RESET after
+ * aac_env_reset / aac_env_auto_reset, STEP after aac_env_step and before any reset; state->N must be
+ * the handle's N.  One launch on ``stream``, capturable. */
+int aac_env_record(aac_env *env, const aac_record_state *state, const aac_record_step *step, void *stream);
 
 /* State export / import (device pointers, each may be NULL to skip).  `start` (double2[E][N]) is
  * the episode start: the reference-path origin of the WGRU variant's cross-track reward

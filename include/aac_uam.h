@@ -79,6 +79,12 @@ void aac_uam_set_reset_compact(int32_t on);
  * keeps it alive while the handle exists.  The copy is enqueued on `stream`. */
 int aac_uam_use_episode_buffer(aac_uam *env, int32_t *episode_dev, void *stream);
 
+/* Flight recorder (aac_record.h): aac_record with E and the state sources of ``step`` (pos, vel, goal,
+ * heading, clouds and the episode counter, wherever aac_uam_use_episode_buffer has put it; no map_idx)
+ * filled from the handle's live device pointers at call time.  The double actions are stored as float.
+ * state->N must be the handle's N.  One launch on ``stream``, capturable. */
+int aac_uam_record(aac_uam *env, const aac_record_state *state, const aac_record_step *step, void *stream);
+
 /* Host: draw n episodes with the reference's rules (UAM/env:575-747, UAM/util:165-237): cloud
  * choices, starts in the two start zones re-drawn until > 3 pB from earlier starts, ends uniform
  * over the no-spawn-subtracted regions on the start's side of the runway. */

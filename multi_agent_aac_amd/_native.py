@@ -20,6 +20,7 @@ EXPORTS = (
     "aac_env_set_od_bank", "aac_env_set_od_banks", "aac_env_auto_reset", "aac_env_set_reset_compact", "aac_env_use_episode_buffer", "aac_env_get_state", "aac_env_set_state",
     "aac_env_band_max", "aac_astar", "aac_od_bank_build",
     "aac_stats_last_error", "aac_stats_accumulate", "aac_stats_reduce",
+    "aac_record_last_error", "aac_record", "aac_env_record", "aac_uam_record",
 )
 
 vp = ctypes.c_void_p
@@ -58,6 +59,26 @@ class StatsStep(ctypes.Structure):         # aac_stats_step
                 ("quota", vp), ("step_index", ctypes.c_int64)]
 
 
+class RecordEpisode(ctypes.Structure):     # aac_record_episode (include/aac_record.h)
+    _fields_ = [("ret", ctypes.c_double), ("min_sep", ctypes.c_double)] + \
+               [(n, i32) for n in ("min_sep_t", "row0", "rows", "len", "episode", "env", "flags", "pad")]
+
+
+class RecordState(ctypes.Structure):       # aac_record_state
+    _fields_ = [("env_ids", vp), ("T", i32), ("S", i32), ("P", i32), ("N", i32)] + \
+               [(n, vp) for n in ("cursor", "ep_seen", "dropped", "run_len", "row0", "run_min_t", "run_flags",
+                                  "run_return", "run_min_sep", "header", "pos", "vel", "goal", "act", "reward",
+                                  "done", "mask", "nearest", "nearest_idx", "min_sep", "heading", "clouds",
+                                  "episodes")]
+
+
+class RecordStep(ctypes.Structure):        # aac_record_step
+    _fields_ = [("phase", i32), ("E", i32)] + \
+               [(n, vp) for n in ("pos", "vel", "goal", "episode", "map_idx", "heading", "clouds", "act", "reward")] + \
+               [("act_f64", i32), ("reward_f64", i32), ("done", vp), ("mask", vp), ("env_done", vp), ("sel", vp),
+                ("return_mode", i32), ("max_episodes", i32)]
+
+
 _lib = None
 
 
@@ -92,6 +113,13 @@ def lib():
         L.aac_stats_last_error.restype = ctypes.c_char_p
         L.aac_stats_accumulate.argtypes = [ctypes.POINTER(StatsState), ctypes.POINTER(StatsStep), vp]
         L.aac_stats_reduce.argtypes = [ctypes.POINTER(StatsState), i32, vp, i32, vp]
+    if hasattr(L, "aac_record") or not os.environ.get("AAC_LIB"):
+        rec = [ctypes.POINTER(RecordState), ctypes.POINTER(RecordStep), vp]
+        L.aac_record_last_error.restype = ctypes.c_char_p
+        L.aac_uam_last_error.restype = ctypes.c_char_p
+        L.aac_record.argtypes = rec
+        L.aac_env_record.argtypes = [vp] + rec
+        L.aac_uam_record.argtypes = [vp] + rec
     for name in EXPORTS:
         if os.environ.get("AAC_LIB") and not hasattr(L, name):
             continue          # an A/B experiment build of an earlier revision

@@ -2092,6 +2092,21 @@ int aac_env_use_episode_buffer(aac_env *h, int32_t *episode_dev, void *stream) {
     return AAC_OK;
 }
 
+int aac_env_record(aac_env *h, const aac_record_state *state, const aac_record_step *step, void *stream) {
+    if (!h || !state || !step) return fail(AAC_E_INVALID, "null argument");
+    if (state->N != h->cfg.N) return fail(AAC_E_INVALID, "env_record: state->N is not the handle's N");
+    aac_record_step p = *step;
+    p.E = h->cfg.E;
+    p.pos = (const double *)h->pos;
+    p.vel = (const double *)h->vel;
+    p.goal = (const double *)h->goal;
+    p.episode = h->episode;
+    p.map_idx = h->map_idx;
+    p.heading = p.clouds = nullptr;
+    if (int rc = aac_record(state, &p, stream)) return fail(rc, aac_record_last_error());
+    return AAC_OK;
+}
+
 #define CPY(dst, src, n)                                                                                  \
     if (dst && src) HIPCHK(hipMemcpyAsync((void *)(dst), (const void *)(src), (n), hipMemcpyDeviceToDevice, \
                                           (hipStream_t)stream));

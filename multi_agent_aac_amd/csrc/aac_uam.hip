@@ -1384,6 +1384,22 @@ int aac_uam_bank_build(int32_t n, int32_t N, uint64_t seed, double *start, doubl
     return AAC_OK;
 }
 
+int aac_uam_record(aac_uam *h, const aac_record_state *state, const aac_record_step *step, void *stream) {
+    if (!h || !state || !step) return ufail(AAC_E_INVALID, "null argument");
+    if (state->N != h->cfg.N) return ufail(AAC_E_INVALID, "uam_record: state->N is not the handle's N");
+    aac_record_step p = *step;
+    p.E = h->cfg.E;
+    p.pos = (const double *)h->pos;
+    p.vel = (const double *)h->vel;
+    p.goal = (const double *)h->goal;
+    p.episode = h->episode;
+    p.map_idx = nullptr;
+    p.heading = h->heading;
+    p.clouds = (const double *)h->clouds;
+    if (int rc = aac_record(state, &p, stream)) return ufail(rc, aac_record_last_error());
+    return AAC_OK;
+}
+
 #define UCPY(dst, src, n)                                                                                   \
     if (dst && src) UCHK(hipMemcpyAsync((void *)(dst), (const void *)(src), (n), hipMemcpyDeviceToDevice,   \
                                         (hipStream_t)stream));

@@ -8,6 +8,9 @@ learner's noise counter and the trainer's captured graphs are never touched, so 
 run between any two training steps.  Every ``evaluate`` call replays the same episode set (the eval
 env's episode counters are zeroed first): common random numbers across checkpoints.
 
+``record`` plays the same episode set with a flight recorder (``record.FlightRecorder``) and also
+returns the flown paths and per-step status as ``record.Trajectories``.
+
 With several ranks each rank evaluates its own envs; the results are not combined.
 """
 import torch
@@ -57,6 +60,7 @@ class Evaluator:
             self._acts = [gru._ActPlan(self.model, self.bufs[p].own, self.bufs[p].radar, self.hp[p], self.hp[1 - p])
                           for p in range(2)]
         self._graphs = None
+        self._rec = self._rec_key = self._rec_graphs = None     # built by the first record()
 
     def _start(self):
         """The eval env at the start of its episode set: counters zeroed, every env redrawn."""
@@ -85,17 +89,40 @@ class Evaluator:
             self.env.step_tail(act, out=n, replay=None)
             self.stats.accumulate(n, quota=self.quota)
 
-    def _capture(self):
+    @torch.no_grad()
+    def _record_step(self, p):
+        """``_step`` as separate launches, so that the recorder sees the terminal state before the reset
+        and the fresh state after it: act, env step, record, tally, zero the finished envs' hidden
+        states, auto-reset, record the reset rows.  Same results as the fused tail."""
+        c, n = self.bufs[p], self.bufs[1 - p]
+        hn = None
+        if self.uam:
+            act = self.model.act(c.own, c.radar, self.episode, noisy=False)
+        elif self.gru:
+            act, hn, _ = self._acts[p](None)
+        else:
+            act = self.model.act(c.own, c.radar, c.nei, self.episode, noisy=False)
+        self.env.step(act, out=n)
+        self._rec.after_step(n, act)
+        self.stats.accumulate(n, quota=self.quota)
+        if hn is not None:
+            from . import gru
+            gru.reset_hidden(hn, n.env_done)
+        self.env.auto_reset(n.env_done, out=n)
+        self._rec.after_reset(n.env_done)
+
+    def _capture(self, step=None):
         # one eager step per parity first: act plans and buffers are built outside the captures
+        step = step or self._step
         self._start()
-        self._step(0)
-        self._step(1)
+        step(0)
+        step(1)
         torch.cuda.synchronize()
         graphs = []
         for p in (0, 1):
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                self._step(p)
+                step(p)
             graphs.append(g)
         return graphs
 
@@ -118,3 +145,43 @@ class Evaluator:
             if (s + 1) % POLL == 0 and self.stats.under_quota() == 0:
                 break
         return self.stats.read()
+
+    def record(self, episodes_per_env=1, env_ids=None, steps=None):
+        """``evaluate(k)`` with a flight recorder on the envs ``env_ids`` (None: all): the same episode
+        set, quota rule and early stop; returns ``(stats, Trajectories)``.  ``steps`` rows are kept per
+        track; the default, k * (episode_length + 2), never drops one.  The rollout runs the split
+        launch sequence (``_record_step``) from a pair of graphs of its own, captured on first use;
+        ``evaluate`` and its graphs are not involved."""
+        steps_run = self._record_rollout(episodes_per_env, env_ids, steps)
+        assert steps_run > 0
+        return self.stats.read(), self._rec.read()
+
+    def _record_rollout(self, episodes_per_env=1, env_ids=None, steps=None):
+        """The device part of ``record``: nothing is downloaded but the poll word.  Returns the number
+        of steps played."""
+        from .record import FlightRecorder
+        k = int(episodes_per_env)
+        assert k >= 1
+        S = int(steps) if steps is not None else k * (self.episode_length + 2)
+        key = (None if env_ids is None else tuple(int(e) for e in env_ids), S, k)
+        if self._rec_key != key:
+            self._rec_graphs = None
+            self._rec = FlightRecorder.for_env(self.env, env_ids, steps=S, episodes=k)
+            self._rec_key = key
+        rec = self._rec
+        use_graph = not _trainer.NO_GRAPH
+        if use_graph and self._rec_graphs is None:
+            self._rec_graphs = self._capture(self._record_step)
+        self._start()
+        self.stats.reset()
+        self.quota.fill_(k)
+        rec.reset()
+        rec.after_reset(None)
+        for s in range(k * (self.episode_length + 1)):
+            if use_graph:
+                self._rec_graphs[s & 1].replay()
+            else:
+                self._record_step(s & 1)
+            if (s + 1) % POLL == 0 and self.stats.under_quota() == 0:
+                break
+        return s + 1
