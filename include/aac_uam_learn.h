@@ -90,6 +90,10 @@ int aac_uam_head(const double *h, int32_t B, const double *w, const double *b, i
 int aac_uam_td_mse_head(const double *ht, const double *wt, const double *bt, const double *rew, const double *done,
                         int32_t ldr, double gamma, double *y, const double *h, const double *w, const double *b,
                         int32_t B, double *dq, double *dh, double *lterm, void *stream);
+/* The same launch that also stores the critic's Q(h[r]) into q[r] (q may be NULL). */
+int aac_uam_td_mse_head_q(const double *ht, const double *wt, const double *bt, const double *rew, const double *done,
+                          int32_t ldr, double gamma, double *y, const double *h, const double *w, const double *b,
+                          int32_t B, double *dq, double *dh, double *lterm, double *q, void *stream);
 /* torch.optim.Adam(fused, capturable) step for float64 parameters: g = sum of nsplit partial
  * copies gpart[s*n + i] in copy order; t = *step + step_add, bias corrections in float64:
  *   m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; p -= (lr/(1-b1^t)) m / (sqrt(v)/sqrt(1-b2^t) + eps) */

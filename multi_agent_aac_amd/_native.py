@@ -21,6 +21,7 @@ EXPORTS = (
     "aac_env_band_max", "aac_astar", "aac_od_bank_build",
     "aac_stats_last_error", "aac_stats_accumulate", "aac_stats_reduce",
     "aac_record_last_error", "aac_record", "aac_env_record", "aac_uam_record",
+    "aac_monitor_last_error", "aac_monitor_vec", "aac_monitor_commit",
 )
 
 vp = ctypes.c_void_p
@@ -79,6 +80,24 @@ class RecordStep(ctypes.Structure):        # aac_record_step
                 ("return_mode", i32), ("max_episodes", i32)]
 
 
+class MonitorVecJob(ctypes.Structure):     # aac_monitor_vec_job (include/aac_monitor.h)
+    _fields_ = [("g", vp), ("param", vp), ("n", ctypes.c_int64), ("gstride", ctypes.c_int64),
+                ("seg_stride", ctypes.c_int64)] + \
+               [(n, i32) for n in ("nsplit", "nseg", "order", "col0", "net", "cols")] + \
+               [("gscale", ctypes.c_double), ("scratch", vp)]
+
+
+class MonitorRows(ctypes.Structure):       # aac_monitor_rows
+    _fields_ = [("p", vp), ("col_stride", ctypes.c_int64), ("row_stride", ctypes.c_int64)]
+
+
+class MonitorCommitArgs(ctypes.Structure):  # aac_monitor_commit_args
+    _fields_ = [(n, MonitorRows) for n in ("q", "y", "q_a", "reward", "qn", "done")] + \
+               [(n, i32) for n in ("done_width", "f64", "A", "B", "R")] + \
+               [("a_off", ctypes.c_double), ("gamma", ctypes.c_double)] + \
+               [(n, vp) for n in ("scratch", "rec", "ring", "ring_update", "agg", "state")]
+
+
 _lib = None
 
 
@@ -120,6 +139,10 @@ def lib():
         L.aac_record.argtypes = rec
         L.aac_env_record.argtypes = [vp] + rec
         L.aac_uam_record.argtypes = [vp] + rec
+    if hasattr(L, "aac_monitor_vec") or not os.environ.get("AAC_LIB"):
+        L.aac_monitor_last_error.restype = ctypes.c_char_p
+        L.aac_monitor_vec.argtypes = [ctypes.POINTER(MonitorVecJob), i32, i32, vp]
+        L.aac_monitor_commit.argtypes = [ctypes.POINTER(MonitorCommitArgs), vp]
     for name in EXPORTS:
         if os.environ.get("AAC_LIB") and not hasattr(L, name):
             continue          # an A/B experiment build of an earlier revision

@@ -242,7 +242,7 @@ __global__ void __launch_bounds__(256) uam_td_mse_head_kernel(const double *__re
                                                               double *y, const double *__restrict__ h,
                                                               const double *__restrict__ w,
                                                               const double *__restrict__ b, int B, double *dqo,
-                                                              double *dh, double *lterm) {
+                                                              double *dh, double *lterm, double *qo) {
     const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= B) return;
     double hv[4];
@@ -254,6 +254,7 @@ __global__ void __launch_bounds__(256) uam_td_mse_head_kernel(const double *__re
     const double dq = (2.0 / B) * e;
     if (lane == 0) lterm[r] = e * e;
     if (dqo && lane == 0) dqo[r] = dq;
+    if (qo && lane == 0) qo[r] = q;          // the critic's Q itself (the learner monitor's rows)
 #pragma unroll
     for (int c = 0; c < 4; ++c) dh[(size_t)r * 256 + lane + 64 * c] = hv[c] > 0.0 ? dq * w[lane + 64 * c] : 0.0;
 }
@@ -513,11 +514,17 @@ int aac_uam_head(const double *h, int32_t B, const double *w, const double *b, i
 int aac_uam_td_mse_head(const double *ht, const double *wt, const double *bt, const double *rew, const double *done,
                         int32_t ldr, double gamma, double *y, const double *h, const double *w, const double *b,
                         int32_t B, double *dq, double *dh, double *lterm, void *stream) {
+    return aac_uam_td_mse_head_q(ht, wt, bt, rew, done, ldr, gamma, y, h, w, b, B, dq, dh, lterm, nullptr, stream);
+}
+
+int aac_uam_td_mse_head_q(const double *ht, const double *wt, const double *bt, const double *rew, const double *done,
+                          int32_t ldr, double gamma, double *y, const double *h, const double *w, const double *b,
+                          int32_t B, double *dq, double *dh, double *lterm, double *q, void *stream) {
     if (B <= 0) return 0;
     if (!ht || !wt || !bt || !rew || !done || !y || !h || !w || !b || !dh || !lterm)
         return lfail("uam_td_mse_head: bad argument");
     hipLaunchKernelGGL(uam_td_mse_head_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, ht, wt, bt, rew,
-                       done, ldr, gamma, y, h, w, b, B, dq, dh, lterm);
+                       done, ldr, gamma, y, h, w, b, B, dq, dh, lterm, q);
     LHIP(hipGetLastError());
     return 0;
 }

@@ -645,6 +645,11 @@ class FusedUpdate:
     DAOB = os.environ.get("AAC_DAOB", "1") == "1"
     def __init__(self, model, replay, B):
         self.m, self.rep, self.B = model, replay, B
+        # the learner monitor (monitor.LearnerMonitor) attached to the model, or None: its launches are
+        # appended behind the Adam and Polyak launches of this plan
+        self.mon = getattr(model, "monitor", None)
+        if self.mon is not None and model.world > 1:
+            raise ValueError("FusedUpdate: the learner monitor supports world == 1 only")
         N, D0, K = model.n_agents, model.D0, model.n_agents - 1
         self.N, self.D0, self.K, self.Din = N, D0, K, D0 + 2
         dev = model.device
@@ -756,6 +761,10 @@ class FusedUpdate:
         # launch with tau = 0 (targets kept bit-exactly: 1 * t + 0 * s) still advances the step counters
         self.post_hold = [lambda: ops.polyak_flat2(m.fc_t.data, m.fc.data, m.critic_optimizer.step_t, m.fa_t.data,
                                                    m.fa.data, m.actor_optimizer.step_t, 0.0, N)]
+        if self.mon is not None:
+            commit = self._mon_commit()
+            self.post.append(commit)
+            self.post_hold.append(commit)
         self.n_launches = len(self.pre) + sum(len(it) for it in self.iters) + len(self.post)
 
     def _adam(self, opt, flat, gpart, ns, step_add):
@@ -763,9 +772,11 @@ class FusedUpdate:
         copies are summed into the shared gradient buffer, all-reduced (SUM) and the Adam launch
         applies the 1 / world."""
         m = self.m
-        if m.world == 1:
-            return [lambda: adam_sum(opt, gpart, ns, step_add, grad_out=flat.grad)]
         critic = opt is m.critic_optimizer
+        if m.world == 1:
+            col = step_add - 1
+            return ([lambda: adam_sum(opt, gpart, ns, step_add, grad_out=flat.grad)]
+                    + self._mon_vec(col if critic else None, None if critic else col))
         return [lambda: sum_partials(flat.grad, gpart, ns),
                 Collective(lambda: m._allreduce_grads(critic=critic, actor=not critic)),
                 lambda: adam_at(opt, step_add, 1.0 / m.world)]
@@ -782,9 +793,33 @@ class FusedUpdate:
                     lambda: sum_partials(m.fc.grad, self.gc, self.SPLIT_CRITIC),
                     Collective(lambda: m._allreduce_grads(critic=True, actor=True)),
                     lambda: adam_at(ca[0], ca[3], gs), lambda: adam_at(aa[0], aa[3], gs)]
+        mon = self._mon_vec(i_critic, i_actor)
         if adam_pair_ok(self.gc, self.ga):
-            return [lambda: adam_sum_pair(ca, aa)]
-        return [lambda: adam_sum(*ca[:4], grad_out=ca[4]), lambda: adam_sum(*aa[:4], grad_out=aa[4])]
+            return [lambda: adam_sum_pair(ca, aa)] + mon
+        return [lambda: adam_sum(*ca[:4], grad_out=ca[4]), lambda: adam_sum(*aa[:4], grad_out=aa[4])] + mon
+
+    def _mon_vec(self, i_critic, i_actor):
+        """The monitor's launch behind an Adam launch: the norms of the critic gradient of iteration
+        i_critic and / or the actor gradient of iteration i_actor (the partial copies the Adam launch just
+        summed, in its order) and of the parameters it just wrote.  [] without a monitor."""
+        if self.mon is None:
+            return []
+        from .monitor import adam4_order
+        m, jobs = self.m, []
+        for col, net, gpart, ns, flat in ((i_critic, 0, self.gc, self.SPLIT_CRITIC, m.fc),
+                                          (i_actor, 1, self.ga, self.SPLIT_ACTOR, m.fa)):
+            if col is not None:
+                jobs.append((gpart, flat.data, dict(n=flat.numel, net=net, col0=col, nsplit=ns,
+                                                    gstride=gpart.shape[-1], order=adam4_order(gpart, ns))))
+        return [self.mon.vec(*jobs)]
+
+    def _mon_commit(self):
+        """The monitor's launch behind the Polyak launch: column i = gradient iteration i, whose rows
+        are batch i of the [N][B] arrays; its reward is agent i's (the TD target's)."""
+        B, N = self.B, self.N
+        rows = {"q": (self.q_c, 0, B, 1), "y": (self.y, 0, B, 1), "q_a": (self.q_a, 0, B, 1),
+                "reward": (self.rew, 0, B * N + 1, N), "qn": (self.qn, 0, B, 1), "done": (self.done, 0, B * N, N)}
+        return self.mon.commit(B, rows, a_off=0.0, gamma=self.m.GAMMA, done_width=N)
 
     def _merged(self, A, C, cs0):
         """Fewer, fuller launches.  The critic step of iteration i+1 reads the critic

@@ -312,6 +312,11 @@ class GruUpdate:
 
     def __init__(self, model, replay, B):
         self.m, self.rep, self.B = model, replay, B
+        # the learner monitor (monitor.LearnerMonitor) attached to the model, or None: its launches go
+        # behind the Adam launches and the soft update of this plan
+        self.mon = getattr(model, "monitor", None)
+        if self.mon is not None and model.world > 1:
+            raise ValueError("GruUpdate: the learner monitor supports world == 1 only")
         # own rows are as wide as the replay stores them (D0 of the ATT env, or d_own for the
         # reference's two-portion states); the networks read their first d_own columns
         N, D0, d = model.n_agents, replay.D0, model.d_own
@@ -351,6 +356,12 @@ class GruUpdate:
         if m.world > 1:     # SUM over the ranks; the Adam launch applies the 1 / world
             L.append(Collective(lambda: m._allreduce(flat)))
         L.append(lambda: fused.adam_at(opt, 1, 1.0 / m.world))
+        if self.mon is not None:
+            # the norms of the N per-agent segments of the flat gradient the Adam launch just read
+            # (one copy, agent-major) and of the parameters it wrote: column i = agent i
+            N = m.n_agents
+            L.append(self.mon.vec((flat.grad, flat.data, dict(n=flat.numel // N, net=0 if flat is m.fc else 1, col0=0,
+                                                              nseg=N, seg_stride=flat.numel // N))))
         return L
 
     def _build(self):
@@ -441,6 +452,12 @@ class GruUpdate:
         # (the Polyak launches also advance the optimisers' step counters)
         L += [lambda: ops.polyak_flat2(m.fc_t.data, m.fc.data, m.critic_optimizer.step_t, m.fa_t.data, m.fa.data,
                                        m.actor_optimizer.step_t, m.tau, 1)]
+        self.i_soft = len(L) - 1          # the soft update's place in the list
+        if self.mon is not None:
+            # column i = agent i of the [B][N] rows; a_loss = 3 - mean Q as ``stats``
+            rows = {"q": (self.q_c, 0, 1, N), "y": (self.y, 0, 1, N), "q_a": (self.q_a, 0, 1, N),
+                    "reward": (b["rew"], 0, 1, N)}
+            L.append(self.mon.commit(B, rows, a_off=3.0))
         self.L = L
         # i_episode % UPDATE_EVERY != 0 (WGRU/maddpg:320): the same launch with tau = 0 keeps the targets
         # bit-exactly (1 * t + 0 * s) and still advances the step counters
@@ -457,9 +474,11 @@ class GruUpdate:
             self.L[0]()
         else:
             self.bidx.copy_(idx.reshape(-1))
-        for op in self.L[1:-1]:
-            op()
-        (self.L[-1] if soft else self.hold)()
+        for k in range(1, len(self.L)):
+            if k == self.i_soft and not soft:
+                self.hold()
+            else:
+                self.L[k]()
 
     def segments(self):
         """The launch list cut at the collectives (kept inline when RCCL can be captured)."""
@@ -587,6 +606,7 @@ class MADDPG:
         self.pg = process_group
         self.world = torch.distributed.get_world_size(process_group) if process_group is not None else 1
         self._plans, self._acts = {}, {}
+        self.monitor = None
         self._graph = None
         self._graph_B = None
         self._last_src = None
@@ -627,6 +647,19 @@ class MADDPG:
         if self.world > 1:
             parallel.allreduce_sum_(flat.grad, self.pg)
 
+    def attach_monitor(self, mon):
+        """Attach (or, with None, detach) a ``monitor.LearnerMonitor`` of n_agents columns: the update
+        plans built from now on carry its launches.  Cached plans and the captured graph are dropped.
+        One rank only."""
+        if mon is not None:
+            if self.world > 1:
+                raise ValueError("attach_monitor: the learner monitor supports world == 1 only")
+            if mon.A != self.n_agents or mon.dtype != torch.float32:
+                raise ValueError(f"attach_monitor: a float32 monitor of {self.n_agents} columns")
+        self.monitor = mon
+        self._plans = {}
+        self._graph = None
+
     def _plan(self, B, rep=None):
         if rep is None:
             rep = self.replay if self.replay is not None else self.memory.dev
@@ -639,6 +672,8 @@ class MADDPG:
         rep = self.replay if self.replay is not None else self.memory.dev
         ts = [self.fa.data, self.fc.data, self.fa_t.data, self.fc_t.data, rep.counter]
         ts += self.actor_optimizer.state() + self.critic_optimizer.state()
+        if self.monitor is not None:      # the capture's warm-up updates leave no record
+            ts += list(self.monitor.tensors().values())
         return ts, [t.clone() for t in ts]
 
     def capture(self, B, warmup=2):

@@ -109,6 +109,7 @@ class MADDPG:
         self._last_src = None
         self._fplans = {}
         self._infer = None
+        self.monitor = None
 
     # ------------------------------------------------------------------ batched API
     def attach_replay(self, capacity, seed=0):
@@ -198,9 +199,26 @@ class MADDPG:
             self._fplans[key] = fused.FusedUpdate(self, rep, B)
         return self._fplans[key]
 
+    def attach_monitor(self, mon):
+        """Attach (or, with None, detach) a ``monitor.LearnerMonitor`` of n_agents columns: the fused
+        plans built from now on carry its launches.  Cached plans and captured graphs are dropped.
+        The monitor observes the fused learner on one rank only."""
+        if mon is not None:
+            if self.world > 1:
+                raise ValueError("attach_monitor: the learner monitor supports world == 1 only")
+            if not self.fused:
+                raise ValueError("attach_monitor: the learner monitor needs the fused learner (fused=True)")
+            if mon.A != self.n_agents or mon.dtype != torch.float32:
+                raise ValueError(f"attach_monitor: a float32 monitor of {self.n_agents} columns")
+        self.monitor = mon
+        self._fplans = {}
+        self._graph = None
+
     def _update_core(self, B, idx_list=None, rep=None, soft=True, freeze_actor=False):
         if rep is None:
             rep = self.replay if self.replay is not None else self.memory.dev
+        if self.monitor is not None and (freeze_actor or not self.fused):
+            raise ValueError("the learner monitor observes the fused learner only (no autograd / frozen-actor update)")
         N = self.n_agents
         idx = None if idx_list is None else torch.cat([i.reshape(-1) for i in idx_list])
         if self.fused and not freeze_actor:     # the frozen-actor phase runs on the autograd path
@@ -224,6 +242,8 @@ class MADDPG:
         rep = self.replay if self.replay is not None else self.memory.dev
         ts = [self.fa.data, self.fc.data, self.fa_t.data, self.fc_t.data, rep.counter]
         ts += self.actor_optimizer.state() + self.critic_optimizer.state()
+        if self.monitor is not None:      # the capture's warm-up updates leave no record
+            ts += list(self.monitor.tensors().values())
         return ts, [t.clone() for t in ts]
 
     def capture(self, B, warmup=2):

@@ -73,6 +73,8 @@ class CheckpointMixin:
             extra["h"] = self.h
         if getattr(self, "stats", None) is not None:
             extra.update({f"stats.{k}": v for k, v in self.stats.tensors().items()})
+        if getattr(self, "monitor", None) is not None:
+            extra.update({f"monitor.{k}": v for k, v in self.monitor.tensors().items()})
         return dict(learner=self.model, replay=self.replay, env=self.env, extra=extra)
 
     def save_checkpoint(self, path):
@@ -96,12 +98,25 @@ class CheckpointMixin:
             from .stats import EpisodeStats
             self.stats = EpisodeStats.for_env(self.env)
 
+    def _init_monitor(self, monitor, A, dtype):
+        """``monitor``: False / None (off), True (a ring of 64 updates) or a ring length.  Built and
+        attached to the model before its first update plan."""
+        self.monitor = None
+        if monitor:
+            from .monitor import LearnerMonitor
+            ring = 64 if monitor is True else int(monitor)
+            self.monitor = LearnerMonitor(A, ring=ring, dtype=dtype, device=self.model.device)
+            self.model.attach_monitor(self.monitor)
+
     def finish(self):
         """End of a run: checks that no launch overflowed the env's exact threshold fix-up list
-        (``env.check_band_capacity``, where the env has one) and returns the episode statistics
-        (``stats.read()``; None without ``stats=True``).  Synchronises."""
+        (``env.check_band_capacity``, where the env has one), that the learner monitor (if any) saw no
+        non-finite update (``monitor.check()``: FloatingPointError naming the update), and returns the
+        episode statistics (``stats.read()``; None without ``stats=True``).  Synchronises."""
         if hasattr(self.env, "check_band_capacity"):
             self.env.check_band_capacity()
+        if getattr(self, "monitor", None) is not None:
+            self.monitor.check()
         return self.stats.read() if self.stats is not None else None
 
 
@@ -114,9 +129,16 @@ class Trainer(CheckpointMixin):
     the whole-step graphs; ``finish()`` returns them.  Off (the default) the launch sequence is
     unchanged and ``self.stats`` is None.  A checkpoint of a stats-enabled trainer carries the tallies
     (``stats.*`` tensors) and resumes them exactly; loading a file saved without them into a
-    stats-enabled trainer raises a KeyError naming the missing tensor and changes nothing."""
+    stats-enabled trainer raises a KeyError naming the missing tensor and changes nothing.
 
-    def __init__(self, E, N, B, memory, radar, seed, pg=None, model="att", maps=1, stats=False):
+    ``monitor=True`` (or a ring length) keeps the learner's records -- per-update losses, Q / target
+    ranges, gradient and parameter norms, a sticky first-non-finite-update word -- on the device in
+    ``self.monitor`` (``monitor.LearnerMonitor``), fed by launches inside every update, eager or
+    captured; ``finish()`` raises FloatingPointError if an update went non-finite.  Off (the default)
+    the launch lists are unchanged and ``self.monitor`` is None.  Its tensors are checkpointed as
+    ``monitor.*`` under the same rules as ``stats.*``."""
+
+    def __init__(self, E, N, B, memory, radar, seed, pg=None, model="att", maps=1, stats=False, monitor=False):
         from . import world
         from .env import BatchedEnv
         from .maddpg import MADDPG
@@ -164,6 +186,7 @@ class Trainer(CheckpointMixin):
         # (no whole-step graph).  tests/oracle_diff.py hooks the C oracle in this way.
         self.pre_step_hooks, self.post_step_hooks = [], []
         self._init_stats(stats)
+        self._init_monitor(monitor, N, torch.float32)
 
     def graph_ok(self):
         """Whole-step graphs: the fused env tail, one rank, the fused learner (ATT: AAC_STEP_GRAPH; the
@@ -219,9 +242,13 @@ class Trainer(CheckpointMixin):
 
     def _graphs_current(self):
         gen = getattr(self.env, "bank_generation", 0)
-        if (self._sg or getattr(self, "_sg2", None)) and getattr(self, "_sg_bank_gen", gen) != gen:
-            self._sg, self._sg2 = {}, {}      # the env's OD bank / seed changed under the captured graphs
-        self._sg_bank_gen = gen
+        mon = self.model.monitor
+        if (self._sg or getattr(self, "_sg2", None)) and (getattr(self, "_sg_bank_gen", gen) != gen
+                                                          or getattr(self, "_sg_mon", mon) is not mon):
+            # the env's OD bank / seed changed, or a learner monitor was attached / detached (new update
+            # plans), under the captured graphs
+            self._sg, self._sg2 = {}, {}
+        self._sg_bank_gen, self._sg_mon = gen, mon
         if self.gru and not self._sg and not getattr(self, "_sg2", None):
             # (re)capture: the hidden-state pair's offset against the buffer parity, as of now
             p = 0 if self.cur is self.bufs[0] else 1
@@ -377,9 +404,11 @@ class UamTrainer(CheckpointMixin):
     """Vectorised UAM/main:361-640 loop on one GPU: actor + noise, env step, one replay row per
     aircraft, GPU auto-reset from the episode bank, one update_myown (one gradient iteration).
     ``stats=True``: episode tallies in ``self.stats``, checkpointed and returned by ``finish()`` as
-    ``Trainer``'s (a file saved without them raises a KeyError naming the tensor on load)."""
+    ``Trainer``'s (a file saved without them raises a KeyError naming the tensor on load).
+    ``monitor=True`` (or a ring length): the learner's records in ``self.monitor`` as ``Trainer``'s (one
+    column, float64)."""
 
-    def __init__(self, E, N, B, memory, seed, pg=None, stats=False):
+    def __init__(self, E, N, B, memory, seed, pg=None, stats=False, monitor=False):
         from . import uam, uam_learner
         self.E, self.N, self.B = E, N, B
         self.gru = False
@@ -402,6 +431,7 @@ class UamTrainer(CheckpointMixin):
         self.pos_dev = torch.zeros(2, dtype=torch.int64, device="cuda")   # ring position ping-pong
         self._pos_dirty = True
         self._init_stats(stats)
+        self._init_monitor(monitor, 1, torch.float64)
 
     def graph_ok(self):
         """Whole-step graphs: one rank, the fused learner, the replay past one batch, no hooks."""

@@ -208,6 +208,7 @@ def _learn_lib():
         L.aac_uam_gather.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
         L.aac_uam_head.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, i32, dbl, vp, vp, vp, vp]
         L.aac_uam_td_mse_head.argtypes = [vp, vp, vp, vp, vp, i32, dbl, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+        L.aac_uam_td_mse_head_q.argtypes = [vp, vp, vp, vp, vp, i32, dbl, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
         L.aac_adam64_sum.argtypes = [vp, vp, i32, vp, vp, i64, dbl, dbl, dbl, dbl, vp, i32, vp]
         L.aac_adam64_sum_scaled.argtypes = [vp, vp, i32, vp, vp, i64, dbl, dbl, dbl, dbl, vp, i32, dbl, vp]
         L.aac_uam_polyak.argtypes = [vp, vp, i64, dbl, vp, vp, vp, i32, vp, vp]
@@ -274,6 +275,11 @@ class FusedUamUpdate:
 
     def __init__(self, m, B, rep):
         self.m, self.B, self.rep = m, int(B), rep
+        # the learner monitor (monitor.LearnerMonitor) attached to the model, or None: its launches go
+        # behind the Adam launches and the soft update of this plan
+        self.mon = getattr(m, "monitor", None)
+        if self.mon is not None and m.world > 1:
+            raise ValueError("FusedUamUpdate: the learner monitor supports world == 1 only")
         dev = m.device
         z = lambda *s: torch.zeros(*s, dtype=F64, device=dev)   # noqa: E731
         fs = m._flat_state()
@@ -294,6 +300,7 @@ class FusedUamUpdate:
         self.ha1, self.ha2, self.hp1, self.hp2 = z(B, 128), z(B, 128), z(B, 128), z(B, 256)
         self.dp1, self.dp2, self.dout, self.dha1, self.dha2 = z(B, 64), z(B, 256), z(B, 2), z(B, 128), z(B, 128)
         self.y, self.dq, self.lq, self.la, self.loss = z(B), z(B), z(B), z(B), z(2)
+        self.q = z(B) if self.mon is not None else None       # the critic's Q rows (monitor only)
         self._launches = self._build()
 
     def _offsets(self, module, base):
@@ -336,6 +343,16 @@ class FusedUamUpdate:
             return lambda: _ok(L.aac_gemm64_batch(arr, n, fused._stream()), "aac_gemm64_batch")
 
         st = self
+        if self.mon is None:
+            td_head = lambda: _ok(L.aac_uam_td_mse_head(  # noqa: E731
+                P(st.hc2t), Wc(ct, "out_feature_q"), Bc(ct, "out_feature_q"), P(R, 27), P(R, 28), ROW, float(m.GAMMA),
+                P(st.y), P(st.hc2), Wc(c, "out_feature_q"), Bc(c, "out_feature_q"), B, P(st.dq), P(st.dh2), P(st.lq),
+                fused._stream()), "aac_uam_td_mse_head")
+        else:       # the same launch, also storing the critic's Q rows for the monitor
+            td_head = lambda: _ok(L.aac_uam_td_mse_head_q(  # noqa: E731
+                P(st.hc2t), Wc(ct, "out_feature_q"), Bc(ct, "out_feature_q"), P(R, 27), P(R, 28), ROW, float(m.GAMMA),
+                P(st.y), P(st.hc2), Wc(c, "out_feature_q"), Bc(c, "out_feature_q"), B, P(st.dq), P(st.dh2), P(st.lq),
+                P(st.q), fused._stream()), "aac_uam_td_mse_head_q")
         launches = [
             # replay sample + gather (UAM/maddpg:330-345)
             lambda: ops.replay_sample(st.rep.meta, B, st.rep.seed, st.rep.counter, st.idx),
@@ -363,10 +380,7 @@ class FusedUamUpdate:
                       RELU)]),
             # TD target r + gamma Q'(s', a')(1 - done) and the mse gradient (UAM/maddpg:346-380), one
             # launch: the critic's head chained on each row's just-computed target
-            lambda: _ok(L.aac_uam_td_mse_head(P(st.hc2t), Wc(ct, "out_feature_q"), Bc(ct, "out_feature_q"), P(R, 27),
-                                              P(R, 28), ROW, float(m.GAMMA), P(st.y), P(st.hc2),
-                                              Wc(c, "out_feature_q"), Bc(c, "out_feature_q"), B, P(st.dq), P(st.dh2),
-                                              P(st.lq), fused._stream()), "aac_uam_td_mse_head"),
+            td_head,
             # critic weight gradients and the backward into the merge layer's input
             gemm([wgrad(P(st.dq), 1, P(st.hc2), 256, 1, 256, gc["out_feature_q.0.weight"], gc["out_feature_q.0.bias"],
                         nC),
@@ -407,6 +421,10 @@ class FusedUamUpdate:
             lambda: _ok(L.aac_uam_polyak(P(T), P(F), nC + nA, float(m.tau), st.step.data_ptr(), P(st.lq), P(st.la),
                                          B, P(st.loss), fused._stream()), "aac_uam_polyak"),
         ]
+        if self.mon is not None:
+            # one column; the reward is column 27 of the gathered replay rows, q_a the policy's Q rows
+            rows = {"q": (st.q, 0, 0, 1), "y": (st.y, 0, 0, 1), "q_a": (st.la, 0, 0, 1), "reward": (R, 27, 0, ROW)}
+            launches.append(self.mon.commit(B, rows, a_off=0.0))
         return launches
 
     def _adam_launches(self, off, n, gpart, lr):
@@ -426,7 +444,13 @@ class FusedUamUpdate:
                                                        st.betas[0], st.betas[1], st.eps, st.step.data_ptr(), 1, gs,
                                                        fused._stream()), "aac_adam64_sum")
         if self.m.world == 1:
-            return [adam(P(gpart), KS)]
+            if self.mon is None:
+                return [adam(P(gpart), KS)]
+            # the norms of the gradient the Adam launch just summed (KS copies in sequence) and of the
+            # parameters it wrote, which live at ``off`` of the shared flat buffer
+            return [adam(P(gpart), KS),
+                    self.mon.vec((gpart, st.flat, dict(n=n, net=0 if off == 0 else 1, col0=0, nsplit=KS, gstride=n,
+                                                       p_off=off)))]
         g = self.gflat[off:off + n]
         m = self.m
         return [lambda: _ok(L.aac_sum64_partials(P(g), P(gpart), KS, n, fused._stream()), "aac_sum64_partials"),
@@ -536,6 +560,7 @@ class MADDPG:
         # update() path on one GPU: the fused float64 learner (FusedUamUpdate), else torch autograd
         self.fused_learner = self.device.type == "cuda" and os.environ.get("AAC_UAM_FUSED", "1") != "0"
         self._fu = None
+        self.monitor = None
         self._fstate = None         # shared flat parameter / Adam state (``_flat_state``)
         self._opt_steps = []
 
@@ -632,6 +657,8 @@ class MADDPG:
         return self._static[key]
 
     def _sampled_core(self, rep, B, idx=None):
+        if self.monitor is not None:
+            raise ValueError("the learner monitor observes the fused learner only (not the torch-autograd update)")
         self._init_grads()
         bidx, rows = self._buffers(rep, B)
         if idx is None:
@@ -682,7 +709,8 @@ class MADDPG:
         rep = replay if replay is not None else (self.replay if self.replay is not None else self.memory.dev)
         if len(rep) < B:
             raise ValueError(f"replay holds {len(rep)} transitions, cannot sample {B} distinct rows")
-        if self.device.type == "cuda" and self.fused_learner and (self.world > 1 or (idx is None and use_graph)):
+        mon = self.monitor is not None      # a monitored update always takes the fused learner (eager too)
+        if self.device.type == "cuda" and self.fused_learner and (self.world > 1 or mon or (idx is None and use_graph)):
             # the fused learner: one graph (world == 1) or one per segment between the gradient
             # all-reduces (world > 1, also for eager calls: the torch path would all-reduce per module)
             fu = self.fused(B, rep)
@@ -736,6 +764,21 @@ class MADDPG:
         self._opt_steps = [st["step"] for opt in (self.critic_optimizer, self.actor_optimizer)
                            for st in opt.state.values()]
         return self._fstate
+
+    def attach_monitor(self, mon):
+        """Attach (or, with None, detach) a one-column float64 ``monitor.LearnerMonitor``: the fused plan
+        built from now on carries its launches; the cached plan and captured graphs are dropped.  One
+        rank and the fused learner only (the torch-autograd update path raises while one is attached)."""
+        if mon is not None:
+            if self.world > 1:
+                raise ValueError("attach_monitor: the learner monitor supports world == 1 only")
+            if not self.fused_learner:
+                raise ValueError("attach_monitor: the learner monitor needs the fused learner")
+            if mon.A != 1 or mon.dtype != F64:
+                raise ValueError("attach_monitor: a float64 monitor of 1 column")
+        self.monitor = mon
+        self._fu = None
+        self._graph = None
 
     def invalidate_graphs(self):
         """Drop every captured update graph (a checkpoint load changed a seed the graphs bake in)."""
