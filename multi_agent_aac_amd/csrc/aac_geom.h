@@ -146,31 +146,10 @@ __device__ __attribute__((always_inline)) bool capsule_crash(double r, const dou
     return false;
 }
 
-// GEOS 64-gon(p, r0) vs 64-gon(q, r1), d = q - p: both share the vertex angles k pi/32, so the
-// Minkowski difference is the 64-gon of circumradius R = r0 + r1 and the shapes meet iff
-// max_k d.n_k <= R cos(pi/64) (touching counts); ``strict``: interiors overlap, i.e. GEOS
-// ``intersects and not touches`` (max_k d.n_k < R cos(pi/64)).  ATT/env:2266-2269 (goal),
-// UAM/env:3933-3936, UAM/util:41-51, :291-297.
-__device__ __attribute__((always_inline)) bool gons_meet(double dx, double dy, double R, bool strict) {
-    const double thr = R * c_tab.apothem;
-    // max_k d.n_k lies in [|d| cos(pi/64), |d|]: outside the band the answer is certain
-    const double dist = sqrt(dx * dx + dy * dy);
-    if (dist > R * (1.0 + 1e-12) + 1e-12) return false;
-    if (dist < thr * (1.0 - 1e-12) - 1e-12) return true;
-    double m = -INFINITY;
-#pragma unroll 8
-    for (int k = 0; k < 64; ++k) {
-        double v = dx * c_tab.nrm_c[k] + dy * c_tab.nrm_s[k];
-        m = v > m ? v : m;
-    }
-    return strict ? m < thr : m <= thr;
-}
-
-
 // ------------------------------------------------------------------ exact threshold predicates
 // The closed forms in this file use the ideal polygons (exact edge normals / apothem); GEOS decides
 // its predicates exactly (DD orientation) on the ROUNDED float vertices, ~1e-13 m away from the ideal
-// ones.  Within EXACT_BAND of a threshold the ATT / OM predicates hand the decision to the exact
+// ones.  Within EXACT_BAND of a threshold the ATT / OM / UAM predicates hand the decision to the exact
 // separating-axis test below on those vertices (oracle/geos.py BAND: the C oracle restates it with
 // 128-bit integers, the tests with rationals).  Orientation signs are exact: the coordinate
 // differences are exact (Sterbenz) when the coordinates of an axis lie within a factor of 2 of each
@@ -300,9 +279,13 @@ __device__ __attribute__((noinline)) int seg_square_meet(double cx, double cy, d
     return und ? -1 : 1;
 }
 
-// the band part of goal_meet_exact (inline, or as the real call goal_band_exact_call)
-__device__ __attribute__((always_inline)) bool goal_band_exact(double px, double py, double gx, double gy, double pb,
-                                                          double dx, double dy, double m, double thr, int km) {
+// the band part of gons_meet_band (inline, or as the real call gons_band_exact_call): 64-gon(p, ra) against
+// 64-gon(g, rb).  strict = false: the closed polygons meet, an edge separates when the other's facing
+// vertices lie strictly outside it; strict = true: the interiors overlap (GEOS ``intersects and not
+// touches``), "on or outside" separates.
+__device__ __attribute__((always_inline)) bool gons_band_exact(double px, double py, double gx, double gy, double ra,
+                                                               double rb, bool strict, double dx, double dy, double m,
+                                                               double thr, int km) {
 #pragma unroll 1
     for (int c = -1; c <= 1; ++c) {
         const int k = (km + c) & 63;
@@ -312,36 +295,43 @@ __device__ __attribute__((always_inline)) bool goal_band_exact(double px, double
 #pragma unroll 1
         for (int j = 0; j < 4; ++j) {         // one orientation at a time (registers: agent phase)
             const bool ea = j < 2;            // j 0, 1: A's edge vs B's vertices; 2, 3: B's edge vs A's
-            const double ox = ea ? px : gx, oy = ea ? py : gy, orr = ea ? pb : 1.0;
-            const double qx0 = ea ? gx : px, qy0 = ea ? gy : py, qr = ea ? 1.0 : pb;
+            const double ox = ea ? px : gx, oy = ea ? py : gy, orr = ea ? ra : rb;
+            const double qx0 = ea ? gx : px, qy0 = ea ? gy : py, qr = ea ? rb : ra;
             const int ie = ea ? ia : ib, iq = ((ea ? ib : ia) + (j & 1)) & 63;
             bool ok;
             const int sg = orient_banded(ox + orr * c_tab.circ_c[ie], oy + orr * c_tab.circ_s[ie],
                                          ox + orr * c_tab.circ_c[(ie + 1) & 63], oy + orr * c_tab.circ_s[(ie + 1) & 63],
                                          qx0 + qr * c_tab.circ_c[iq], qy0 + qr * c_tab.circ_s[iq], ok);
-            if (!ok) return m <= thr;         // undecidable: the closed form
-            if (sg <= 0) sep &= ea ? ~1 : ~2;
+            if (!ok) return strict ? m < thr : m <= thr;         // undecidable: the closed form
+            if (strict ? sg < 0 : sg <= 0) sep &= ea ? ~1 : ~2;
         }
         if (sep) return false;
     }
     return true;
 }
 
-__device__ __attribute__((noinline)) bool goal_band_exact_call(double px, double py, double gx, double gy, double pb,
-                                                                double dx, double dy, double m, double thr, int km) {
-    return goal_band_exact(px, py, gx, gy, pb, dx, dy, m, thr, km);
+__device__ __attribute__((noinline)) bool gons_band_exact_call(double px, double py, double gx, double gy, double ra,
+                                                               double rb, bool strict, double dx, double dy, double m,
+                                                               double thr, int km) {
+    return gons_band_exact(px, py, gx, gy, ra, rb, strict, dx, dy, m, thr, km);
 }
 
-// 64-gon(p, pb) meets 64-gon(g, 1) (ATT/env:2266-2269): gons_meet's closed form, and within EXACT_BAND
-// of the threshold the exact test on the float vertices.  Both rings have their edge normals at the
-// angles (k + 1/2) pi/32, so the axis n_k separates them (ideally) iff d.n_k > (pb + 1) cos(pi/64): only
-// the normals within 1e-6 of the maximum projection m (at most two adjacent ones) can separate the
-// float polygons, by the A edge with outward normal n_k (vertices 63 - k, 64 - k) or the B edge facing
-// it; the exact test checks each against the two vertices of the other's facing edge (the other
-// vertices lie >= 1 (cos(pi/64) - cos(3 pi/64)) = 0.0096 m further out)
+// 64-gon(p, ra) meets 64-gon(g, rb) (ATT/env:2266-2269 goal; UAM/env:3933-3936 goal, UAM/util:41-51 target
+// switch, :291-297 clouds), d = g - p.  Both share the vertex angles k pi/32, so the Minkowski difference
+// is the 64-gon of circumradius R = ra + rb: the closed shapes meet iff max_k d.n_k <= R cos(pi/64), their
+// interiors overlap (``strict``: GEOS ``intersects and not touches``) iff it is < that.  This closed form
+// decides, and within EXACT_BAND of the threshold the exact test on the float vertices.  Both rings have their edge normals at the angles (k + 1/2) pi/32, so the
+// axis n_k separates them (ideally) iff d.n_k > (ra + rb) cos(pi/64): only the normals within 1e-6 of
+// the maximum projection m (at most two adjacent ones) can separate the float polygons, by the A edge
+// with outward normal n_k (vertices 63 - k, 64 - k) or the B edge facing it; the exact test checks each
+// against the two vertices of the other's facing edge (the other vertices lie >= r (cos(pi/64) -
+// cos(3 pi/64)) = 0.0096 r further out, r >= 0.5).  An orientation whose coordinate differences round is
+// undecidable and keeps the closed form: that needs touching vertices more than a factor 2 apart in a
+// coordinate, which cannot happen inside [4, 36] with radii <= 3 (nor in the ATT / OM world).
 template <bool COLD>
-__device__ __attribute__((always_inline)) bool goal_meet_exact(double px, double py, double gx, double gy, double pb) {
-    const double dx = gx - px, dy = gy - py, R = pb + 1.0;
+__device__ __attribute__((always_inline)) bool gons_meet_band(double px, double py, double gx, double gy, double ra,
+                                                              double rb, bool strict) {
+    const double dx = gx - px, dy = gy - py, R = ra + rb;
     const double thr = R * c_tab.apothem;
     const double dist = sqrt(dx * dx + dy * dy);
     if (dist > R * (1.0 + 1e-12) + 1e-12) return false;
@@ -356,8 +346,39 @@ __device__ __attribute__((always_inline)) bool goal_meet_exact(double px, double
     }
     if (m > thr + EXACT_BAND) return false;
     if (m < thr - EXACT_BAND) return true;
-    return COLD ? goal_band_exact_call(px, py, gx, gy, pb, dx, dy, m, thr, km)
-                : goal_band_exact(px, py, gx, gy, pb, dx, dy, m, thr, km);
+    return COLD ? gons_band_exact_call(px, py, gx, gy, ra, rb, strict, dx, dy, m, thr, km)
+                : gons_band_exact(px, py, gx, gy, ra, rb, strict, dx, dy, m, thr, km);
+}
+
+// 64-gon(p, pb) meets 64-gon(g, 1), touching counts (the ATT goal)
+template <bool COLD>
+__device__ __attribute__((always_inline)) bool goal_meet_exact(double px, double py, double gx, double gy, double pb) {
+    return gons_meet_band<COLD>(px, py, gx, gy, pb, 1.0, false);
+}
+
+// interiors of the GEOS 64-gon(p, r) and the rectangle [x0, x1] x [y0, y1] overlap, exactly on the float
+// vertices, in the style of gon_square_meet: the rectangle's axes against the 64-gon's extreme vertices
+// (0: max x, 16: min y, 32: min x, 48: max y), then each 64-gon edge against the rectangle corner nearest to
+// it; a corner on or outside an edge separates (touching is no overlap).  1 / 0, -1 undecidable.  A real
+// call: only the band reaches it.
+__device__ __attribute__((noinline)) int gon_rect_overlap_exact(double px, double py, double r, double x0, double x1,
+                                                                double y0, double y1) {
+    if (px + r * c_tab.circ_c[32] >= x1 || px + r * c_tab.circ_c[0] <= x0 || py + r * c_tab.circ_s[16] >= y1 ||
+        py + r * c_tab.circ_s[48] <= y0)
+        return 0;
+    int und = 0;
+#pragma unroll 1
+    for (int i = 0; i < 64; ++i) {
+        const int k = 63 - i;            // edge i -> i + 1 has the outward normal of index 63 - i
+        const double qx = c_tab.nrm_c[k] > 0.0 ? x0 : x1, qy = c_tab.nrm_s[k] > 0.0 ? y0 : y1;
+        const int i1 = (i + 1) & 63;
+        bool ok;
+        const int sg = orient_banded(px + r * c_tab.circ_c[i], py + r * c_tab.circ_s[i], px + r * c_tab.circ_c[i1],
+                                     py + r * c_tab.circ_s[i1], qx, qy, ok);
+        if (!ok) und = 1;
+        else if (sg >= 0) return 0;      // the nearest corner, hence the rectangle, on or outside this edge
+    }
+    return und ? -1 : 1;
 }
 
 // Cyrus-Beck entry of segment c->e into the clockwise GEOS 64-gon of radius r at p.  EX = 1 (the ATT / OM

@@ -231,18 +231,31 @@ __device__ bool ray_hseg(double cx, double cy, double ex, double ey, double ly, 
     return true;
 }
 
-// interiors of 64-gon(p, r) and the rectangle centred p + (dx, dy) with half sizes hx, hy overlap
-// (polygons_single_cloud_conflict vs the runway, UAM/util:291-297, UAM/env:4095-4106)
-__device__ bool gon_rect_overlap(double dx, double dy, double hx, double hy, double r) {
-    if (fabs(dx) >= hx + r || fabs(dy) >= hy + r) return false;
+// interiors of 64-gon(p, r) and the rectangle rw = (x0, x1, y0, y1) overlap
+// (polygons_single_cloud_conflict vs the runway, UAM/util:291-297, UAM/env:4095-4106): separating axes
+// of the ideal shapes, the rectangle's and the 32 distinct edge normals; touching is no overlap.  An axis
+// within EXACT_BAND of separating hands the decision to the exact test on the float vertices
+// (gon_rect_overlap_exact, a real call); undecidable there (not inside [4, 36]) keeps the closed form.
+__device__ bool gon_rect_overlap(double px, double py, double r, const double *rw) {
+    const double hx = (rw[1] - rw[0]) / 2, hy = (rw[3] - rw[2]) / 2;
+    const double dx = (rw[0] + rw[1]) / 2 - px, dy = (rw[2] + rw[3]) / 2 - py;
+    if (fabs(dx) > hx + r + EXACT_BAND || fabs(dy) > hy + r + EXACT_BAND) return false;
+    bool unsure = fabs(dx) >= hx + r - EXACT_BAND || fabs(dy) >= hy + r - EXACT_BAND;
+    bool closed = !(fabs(dx) >= hx + r || fabs(dy) >= hy + r);
     const double ox = fmax(fabs(dx) - hx, 0.0), oy = fmax(fabs(dy) - hy, 0.0);
     const double dist = sqrt(ox * ox + oy * oy);
-    if (dist > r * (1.0 + 1e-12) + 1e-12) return false;
-    if (dist < r * c_tab.apothem * (1.0 - 1e-12) - 1e-12) return true;
+    if (dist > r * (1.0 + 1e-12) + EXACT_BAND) return false;
+    if (!unsure && dist < r * c_tab.apothem * (1.0 - 1e-12) - EXACT_BAND) return true;
     for (int k = 0; k < 32; ++k) {
         const double proj = fabs(dx * c_tab.nrm_c[k] + dy * c_tab.nrm_s[k]);
         const double lim = hx * fabs(c_tab.nrm_c[k]) + hy * fabs(c_tab.nrm_s[k]) + r * c_tab.apothem;
-        if (proj >= lim) return false;
+        if (proj > lim + EXACT_BAND) return false;
+        unsure |= proj >= lim - EXACT_BAND;
+        closed &= !(proj >= lim);
+    }
+    if (unsure) {
+        const int m = gon_rect_overlap_exact(px, py, r, rw[0], rw[1], rw[2], rw[3]);
+        return m < 0 ? closed : m != 0;
     }
     return true;
 }
@@ -711,7 +724,7 @@ __global__ void __launch_bounds__(BLOCK, AAC_UAM_MIN_WAVES) uam_step_kernel(UArg
                 // at pos; it meets target.buffer(0.5) -> next preset point (UAM/util:41-51)
                 int tg = A.cloud_tgt[eq];
                 const double *pt = c_world.path[kind][tg];
-                if (gons_meet(pt[0] - c.x, pt[1] - c.y, c_world.radius[1] + 0.5, false)) {
+                if (gons_meet_band<true>(c.x, c.y, pt[0], pt[1], c_world.radius[1], 0.5, false)) {
                     tg = (c_world.path_first[kind][tg] + 1) % 6;
                     A.cloud_tgt[eq] = tg;
                 }
@@ -774,9 +787,11 @@ __global__ void __launch_bounds__(BLOCK, AAC_UAM_MIN_WAVES) uam_step_kernel(UArg
 
     // ---- (4) observation; the goal touch of every aircraft first (UAM/env:3929-3936)
     observe_phase(A, S, e0, nag, nullptr);
+    int goal = 0;       // 64-gon(p, pB) touches 64-gon(goal, 1); ss_reward asks again per aircraft: same inputs
     if (active) {
         const double2 g = S.goal[t];
-        if (gons_meet(g.x - np.x, g.y - np.y, A.pb + 1.0, false)) S.reach[t] = 1;
+        goal = gons_meet_band<true>(np.x, np.y, g.x, g.y, A.pb, 1.0, false);
+        if (goal) S.reach[t] = 1;
     }
     __syncthreads(); USTAMP(5);
 
@@ -803,15 +818,13 @@ __global__ void __launch_bounds__(BLOCK, AAC_UAM_MIN_WAVES) uam_step_kernel(UArg
         int cloud = 0;
         if (!me) {
             const double *rw = c_world.runway;
-            cloud = gon_rect_overlap((rw[0] + rw[1]) / 2 - px, (rw[2] + rw[3]) / 2 - py, (rw[1] - rw[0]) / 2,
-                                     (rw[3] - rw[2]) / 2, pb);
+            cloud = gon_rect_overlap(px, py, pb, rw);
             for (int k = 0; k < 2 && !cloud; ++k) {
                 const double2 c = S.cl[le][k];
-                cloud = gons_meet(c.x - px, c.y - py, pb + c_world.radius[k], true);
+                cloud = gons_meet_band<true>(px, py, c.x, c.y, pb, c_world.radius[k], true);
             }
         }
         const double2 g = S.goal[t];
-        const int goal = gons_meet(g.x - px, g.y - py, pb + 1.0, false);
         // dist_to_goal = 5 (1 - total_length_to_end_of_line(pos, ref_line) / L)  (UAM/env:4202-4208)
         const double2 s = A.start[ai];
         const double L = gdist(g.x, g.y, s.x, s.y);
@@ -860,51 +873,55 @@ __global__ void __launch_bounds__(BLOCK, AAC_UAM_MIN_WAVES) uam_step_kernel(UArg
     // exact, so aircraft j's coefficients are 2.0 and 50.0 times 2^(doublings among aircraft 0..j):
     // an inclusive prefix count over the row (ballot + popcount) instead of the sequential walk.
     if (N <= 16) {
-        const int q = t >> 4, j = t & 15;
-        const int eq = e0 + q;
-        const bool on = q < A.epb && eq < A.E && j < N;     // q uniform per row
-        const int la = q * N + j;
-        uint8_t fl = 0, kind = 4, rch = 1;
-        if (on) {
-            fl = S.flag[la];
-            kind = S.kind[la];
-            rch = S.reach[la];
-        }
-        const unsigned long long dbl_nd = __ballot(on && (fl & 1) && (fl & 2));
-        const unsigned long long dbl_cr = __ballot(on && kind == 2 && (fl & 4));
-        const int sh = 16 * ((t >> 4) & 3);
-        const unsigned long long upto = ((2ull << j) - 1) << sh, row = 0xffffull << sh;
-        const double ndc = ldexp(2.0, __popcll(dbl_nd & upto));
-        const double crash = ldexp(50.0, __popcll(dbl_cr & upto));
-        int dn = 0;
-        if (on) {
-            const double nd = (fl & 1) ? ndc * S.nd_val[la] : ndc * 0;
-            double rew;
-            dn = 1;
-            if (kind == 0 || kind == 1 || kind == 2) {
-                rew = 0 - crash;
-            } else if (kind == 3) {
-                rew = 0 + 50.0 + 0;
-                dn = 0;
-            } else {
-                rew = S.base[la] - nd;
-                dn = 0;
+        // N < 4 puts more than BLOCK / 16 = 16 envs in a workgroup: the rows take them 16 at a time (a
+        // uniform trip count: every lane joins the ballots)
+        for (int q0 = 0; q0 < A.epb; q0 += BLOCK / 16) {
+            const int q = q0 + (t >> 4), j = t & 15;
+            const int eq = e0 + q;
+            const bool on = q < A.epb && eq < A.E && j < N;     // q uniform per row
+            const int la = q * N + j;
+            uint8_t fl = 0, kind = 4, rch = 1;
+            if (on) {
+                fl = S.flag[la];
+                kind = S.kind[la];
+                rch = S.reach[la];
             }
-            const size_t aj = (size_t)eq * N + j;
-            A.reward[aj] = rew;
-            A.done[aj] = (uint8_t)dn;
-        }
-        const unsigned long long m_done = __ballot(on && dn), m_nreach = __ballot(on && !rch);
-        const unsigned long long m_k0 = __ballot(on && kind == 0), m_k1 = __ballot(on && kind == 1);
-        const unsigned long long m_k2 = __ballot(on && kind == 2), m_k3 = __ballot(on && kind == 2 && (fl & 8));
-        if (on && j == 0) {
-            A.bbc[4 * eq + 0] = (m_k0 & row) != 0;
-            A.bbc[4 * eq + 1] = (m_k1 & row) != 0;
-            A.bbc[4 * eq + 2] = (m_k2 & row) != 0;
-            A.bbc[4 * eq + 3] = (m_k3 & row) != 0;
-            const int st = A.step[eq] + 1;
-            A.step[eq] = st;
-            A.env_done[eq] = (uint8_t)((A.episode_length < st) || (m_done & row) != 0 || (m_nreach & row) == 0);
+            const unsigned long long dbl_nd = __ballot(on && (fl & 1) && (fl & 2));
+            const unsigned long long dbl_cr = __ballot(on && kind == 2 && (fl & 4));
+            const int sh = 16 * ((t >> 4) & 3);
+            const unsigned long long upto = ((2ull << j) - 1) << sh, row = 0xffffull << sh;
+            const double ndc = ldexp(2.0, __popcll(dbl_nd & upto));
+            const double crash = ldexp(50.0, __popcll(dbl_cr & upto));
+            int dn = 0;
+            if (on) {
+                const double nd = (fl & 1) ? ndc * S.nd_val[la] : ndc * 0;
+                double rew;
+                dn = 1;
+                if (kind == 0 || kind == 1 || kind == 2) {
+                    rew = 0 - crash;
+                } else if (kind == 3) {
+                    rew = 0 + 50.0 + 0;
+                    dn = 0;
+                } else {
+                    rew = S.base[la] - nd;
+                    dn = 0;
+                }
+                const size_t aj = (size_t)eq * N + j;
+                A.reward[aj] = rew;
+                A.done[aj] = (uint8_t)dn;
+            }
+            const unsigned long long m_done = __ballot(on && dn), m_nreach = __ballot(on && !rch);
+            const unsigned long long m_k0 = __ballot(on && kind == 0), m_k1 = __ballot(on && kind == 1);
+            const unsigned long long m_k2 = __ballot(on && kind == 2), m_k3 = __ballot(on && kind == 2 && (fl & 8));
+            if (on && j == 0) {
+                A.bbc[4 * eq + 0] = (m_k0 & row) != 0;
+                A.bbc[4 * eq + 1] = (m_k1 & row) != 0;
+                A.bbc[4 * eq + 2] = (m_k2 & row) != 0;
+                A.bbc[4 * eq + 3] = (m_k3 & row) != 0;
+                const int st = A.step[eq] + 1;
+                A.step[eq] = st;
+                A.env_done[eq] = (uint8_t)((A.episode_length < st) || (m_done & row) != 0 || (m_nreach & row) == 0);
+            }
         }
     } else if (t < A.epb && e0 + t < A.E) {
         const int eq = e0 + t, bq = t * N;

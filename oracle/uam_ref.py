@@ -5,9 +5,12 @@ TEST INFRASTRUCTURE ONLY (see oracle/__init__.py).
 section 0); ``UAM/env`` is its ``env_simulator_*.py``, ``UAM/util`` its ``Utilities_own_*.py``,
 ``UAM/main`` its ``ma_main_*.py``.  One object per agent / cloud, per-agent loops, numpy and
 ``math`` exactly where the reference calls them.  Shapely/GEOS calls are replaced by the GEOS
-construction of ``oracle.geos`` and predicates that are exact on those float vertices (closed
-forms exact in real arithmetic, cross-checked by tests against exact rational arithmetic on the
-float vertices (``*_exact``).
+construction of ``oracle.geos`` and predicates that are exact on those float vertices: closed
+forms, exact in real arithmetic for the ideal polygons, decide away from a threshold; within
+``geos.BAND`` / ``geos.BAND_T`` of one the exact rational tests on the float vertices (``*_exact``,
+``geos._seg_seg_first_t_exact``) decide, as GEOS does.  The kernel has the closed forms' arithmetic
+and its own exact band tests (csrc/aac_geom.h); tests/uam_thresholds.py holds both to the exact
+predicates on states built on every threshold.
 
 Followed line by line (default flags of UAM/main:60-100: training mode, evaluation flags off,
 include_other_AC = True, full_observable_critic_flag = False, use_nearestN_neigh_wRadar = False):
@@ -138,9 +141,13 @@ def _max_normal(dx, dy):
 
 def _exact_sat(A, B, strict):
     """Closed convex polygons A, B: strict=False -> they intersect (touching counts);
-    strict=True -> their interiors intersect.  Exact rational separating-axis test."""
+    strict=True -> their interiors intersect.  Exact separating-axis test: the float coordinates
+    are dyadic rationals, so scaled by their largest denominator they are integers."""
     A = [geos._fr(p) for p in A]
     B = [geos._fr(p) for p in B]
+    den = max(v.denominator for P in (A, B) for p in P for v in p)
+    A = [(int(x * den), int(y * den)) for x, y in A]
+    B = [(int(x * den), int(y * den)) for x, y in B]
     for P in (A, B):
         n = len(P)
         for k in range(n):
@@ -160,8 +167,10 @@ def gons_meet(c0, r0, c1, r1, strict=False):
     """GEOS 64-gon(c0, r0) vs 64-gon(c1, r1): ``intersects`` (strict=False) or interiors overlap,
     i.e. ``intersects and not touches`` (strict=True).  Both share the vertex angles k pi/32, so
     the Minkowski difference is the 64-gon of circumradius R = r0 + r1: max_k d.n_k vs
-    R cos(pi/64).  Closed form, same arithmetic as ``gons_meet`` in csrc/aac_geom.h;
-    ``gons_meet_exact`` is the independent check on the float vertices."""
+    R cos(pi/64).  The closed form (same arithmetic as ``gons_meet_band`` in csrc/aac_geom.h)
+    speaks of the ideal polygons; GEOS decides on the rounded float vertices, ~1e-14 m away.
+    Within ``geos.BAND`` of the threshold the exact test on those vertices (``gons_meet_exact``)
+    decides, as ``geos.goal_reached`` does for the ATT goal."""
     dx, dy = c1[0] - c0[0], c1[1] - c0[1]
     R = r0 + r1
     thr = R * APO
@@ -171,7 +180,11 @@ def gons_meet(c0, r0, c1, r1, strict=False):
     if dist < thr * (1.0 - 1e-12) - 1e-12:
         return True
     m = _max_normal(dx, dy)
-    return m < thr if strict else m <= thr
+    if m > thr + geos.BAND:
+        return False
+    if m < thr - geos.BAND:
+        return True
+    return gons_meet_exact(c0, r0, c1, r1, strict)
 
 
 def gons_meet_exact(c0, r0, c1, r1, strict=False):
@@ -182,22 +195,30 @@ def gon_rect_overlap(c, r, rect):
     """Interiors of 64-gon(c, r) and the rectangle (x0, x1, y0, y1) overlap
     (``polygons_single_cloud_conflict``, UAM/util:291-297; the rectangle cannot lie within the
     0.5 circle).  Separating axes: the rectangle's (the 64-gon reaches r along x / y) and the 32
-    distinct 64-gon edge normals (reach r cos(pi/64)); touching is no overlap.  Same arithmetic
-    as ``gon_rect_overlap`` in csrc/aac_uam.hip; ``gon_rect_overlap_exact`` checks it."""
+    distinct 64-gon edge normals (reach r cos(pi/64)); touching is no overlap.  The closed form
+    has the arithmetic of ``gon_rect_overlap`` in csrc/aac_uam.hip; an axis within ``geos.BAND``
+    of separating hands the decision to ``gon_rect_overlap_exact`` on the float vertices."""
     x0, x1, y0, y1 = rect
     hx, hy = (x1 - x0) / 2, (y1 - y0) / 2
     dx, dy = (x0 + x1) / 2 - c[0], (y0 + y1) / 2 - c[1]
-    if abs(dx) >= hx + r or abs(dy) >= hy + r:
+    if abs(dx) > hx + r + geos.BAND or abs(dy) > hy + r + geos.BAND:
         return False
+    unsure = abs(dx) >= hx + r - geos.BAND or abs(dy) >= hy + r - geos.BAND
     ox, oy = max(abs(dx) - hx, 0.0), max(abs(dy) - hy, 0.0)
     dist = math.sqrt(ox * ox + oy * oy)
-    if dist > r * (1.0 + 1e-12) + 1e-12:
+    if dist > r * (1.0 + 1e-12) + geos.BAND:
         return False
-    if dist < r * APO * (1.0 - 1e-12) - 1e-12:
+    if not unsure and dist < r * APO * (1.0 - 1e-12) - geos.BAND:
         return True
     for nx, ny in NORMALS[:32]:
-        if abs(dx * nx + dy * ny) >= hx * abs(nx) + hy * abs(ny) + r * APO:
+        proj = abs(dx * nx + dy * ny)
+        lim = hx * abs(nx) + hy * abs(ny) + r * APO
+        if proj > lim + geos.BAND:
             return False
+        if proj >= lim - geos.BAND:
+            unsure = True
+    if unsure:
+        return gon_rect_overlap_exact(c, r, rect)
     return True
 
 
@@ -209,24 +230,38 @@ def gon_rect_overlap_exact(c, r, rect):
 def _seg_hits(c, e, ring):
     """Nearest intersection of segment c->e with the closed polyline ``ring`` (GEOS
     ``LineString.intersection(polygon.boundary)`` + ``LineString([c, p]).length``), or None.
-    Parallel edges (collinear overlaps, measure zero) are skipped, as the reference skips
-    non-point results."""
+    The rounded parameters t (along the ray) and s (along the edge) decide away from their ends.
+    An edge with t or s within ``geos.BAND_T`` of 0 or 1 -- a ray through a vertex, starting on
+    the boundary, or passing an ulp beside a corner -- and an edge parallel to the ray (a
+    collinear overlap enters at its first point, as ``geos.ray_square_crossing`` has it) are
+    decided by the exact intersection of the two closed segments on the float coordinates."""
     best = None
     dx, dy = e[0] - c[0], e[1] - c[1]
     n = len(ring)
+    BT = geos.BAND_T
     for k in range(n):
         v, w = ring[k], ring[(k + 1) % n]
         ex, ey = w[0] - v[0], w[1] - v[1]
         den = dx * ey - dy * ex
-        if den == 0.0:
-            continue
         qx, qy = v[0] - c[0], v[1] - c[1]
-        t = (qx * ey - qy * ex) / den
-        s = (qx * dy - qy * dx) / den
-        if 0.0 <= t <= 1.0 and 0.0 <= s <= 1.0:
-            d = geos.point_dist(c[0] + t * dx, c[1] + t * dy, c[0], c[1])
-            if best is None or d < best:
-                best = d
+        if den == 0.0:
+            band = True
+        else:
+            t = (qx * ey - qy * ex) / den
+            s = (qx * dy - qy * dx) / den
+            if not (-BT <= t <= 1.0 + BT and -BT <= s <= 1.0 + BT):
+                continue
+            band = min(abs(t), abs(t - 1.0), abs(s), abs(s - 1.0)) <= BT
+        if band:
+            C, V, W = geos._fr(c), geos._fr(v), geos._fr(w)
+            E = geos._fr(e)
+            tx = geos._seg_seg_first_t_exact(C, (E[0] - C[0], E[1] - C[1]), V, W)
+            if tx is None:
+                continue
+            t = float(tx)
+        d = geos.point_dist(c[0] + t * dx, c[1] + t * dy, c[0], c[1])
+        if best is None or d < best:
+            best = d
     return best
 
 

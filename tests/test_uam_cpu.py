@@ -15,7 +15,8 @@ from oracle import uam_ref as U
 
 def test_closed_forms_vs_exact():
     """gons_meet (touching counts / strict) and gon_rect_overlap agree with the exact
-    separating-axis test on the GEOS float vertices away from a 1e-9 band of the threshold."""
+    separating-axis test on the GEOS float vertices, everywhere: inside the 1e-9 band of the
+    threshold the exact test decides for them (tests/test_uam_thresholds_cpu.py sits on it)."""
     rng = np.random.default_rng(0)
     n = 0
     for _ in range(40):
@@ -24,9 +25,6 @@ def test_closed_forms_vs_exact():
             ang = rng.uniform(0, 2 * math.pi)
             rr = (0.5 + R) * rng.uniform(0.97, 1.03)
             q = c + rr * np.array([math.cos(ang), math.sin(ang)])
-            m = max(abs((q - c) @ np.array(nv)) for nv in U.NORMALS) - (0.5 + R) * U.APO
-            if abs(m) < 1e-9:
-                continue
             assert U.gons_meet(c, 0.5, q, R, strict) == U.gons_meet_exact(c, 0.5, q, R, strict)
             n += 1
         p = np.array([rng.uniform(17, 23), rng.uniform(9, 31)])

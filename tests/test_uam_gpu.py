@@ -128,6 +128,14 @@ def test_uam_step_matches_oracle_n3_long(native_lib):
     _stepped_pair(3, 8, 11, 25, act_scale=0.6)
 
 
+@pytest.mark.parametrize("N", [3, 2])
+def test_uam_step_more_than_16_envs_per_workgroup(native_lib, N):
+    """N < 4 puts floor(64 / N) > 16 envs in a workgroup, more than the 16 rows of 16 lanes that the
+    per-env reward pass has: the envs past the 16th of each workgroup (here 16..20 and 37..41, or
+    16..31) get their reward, done, bbc, env_done and step counter like the others."""
+    _stepped_pair(N, 44, 40 + N, 2)
+
+
 @pytest.mark.parametrize("N", [16, 4])
 def test_uam_tdcpa_branches(native_lib, N):
     """tdCPA (UAM/util:916-938) on injected states built to hit every branch: pairs flying with
