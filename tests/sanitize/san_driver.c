@@ -14,6 +14,63 @@ static double urand(void) {
     return (double)(lcg >> 11) * (1.0 / 9007199254740992.0);
 }
 
+/* The WGRU removal mask at the int32 edge (oracle/aac_oracle.c wgru_reward): lists of cnt = W waypoints with
+ * W = 32 (bit 31: wp_cur negative as int32) and W = 4.  Per env, every agent alike: 0 pops the last entry from
+ * an empty mask (sets the top bit); 1 starts with the top bit set and pops entry 0; 2 has all but entries 0 and
+ * W - 2 removed and pops entry 0; 3 has the top bit set and nothing in reach.  Returns 0 when the masks and
+ * goals after three steps are the expected ones. */
+static int wgru_mask_edge(const uint8_t *occ, const double *bound, int W) {
+    enum { E = 4, N = 3, K = N - 1, D0 = 6 };
+    oc_cfg cfg = {E, N, W, 1, 1, 0, 150, 23, 13, {bound[0], bound[1], bound[2], bound[3]}, occ, 1, 1, 10.0};
+    double *pos = calloc(E * N * 2, 8), *vel = calloc(E * N * 2, 8), *ppos = calloc(E * N * 2, 8);
+    double *pvel = calloc(E * N * 2, 8), *goal = calloc(E * N * 2, 8), *wp = calloc((size_t)E * N * W * 2, 8);
+    double *st = calloc(E * N * 2, 8);
+    int32_t *cur = calloc(E * N, 4), *wc = calloc(E * N, 4), *wall = calloc(E * N, 4), *stp = calloc(E, 4);
+    int32_t *midx = calloc(E, 4);
+    uint8_t *reach = calloc(E * N, 1);
+    oc_state s = {pos, vel, ppos, pvel, goal, wp, cur, wc, reach, wall, stp, midx, st};
+    float *own = calloc(E * N * D0, 4), *radar = calloc(E * N * NRAY, 4), *nei = calloc(E * N * K * 6, 4);
+    float *rew = calloc(E * N, 4), *act = calloc(E * N * 2, 4);
+    uint8_t *done = calloc(E * N, 1), *mask = calloc(E * N, 1), *edone = calloc(E, 1), *bbc = calloc(E * 4, 1);
+    oc_out out = {own, radar, nei, rew, done, mask, edone, bbc, NULL, NULL, NULL, NULL};
+    const uint32_t top = 1u << (W - 1), all = W >= 32 ? 0xffffffffu : (1u << W) - 1u;
+    const uint32_t m0[E] = {0u, top, all & ~(1u | (1u << (W - 2))), top};
+    const int near[E] = {W - 1, 0, 0, -1};
+    const uint32_t want[E] = {top, top | 1u, all & ~(1u << (W - 2)), top};
+    const int last[E] = {W - 2, W - 2, W - 2, W - 2};
+    for (int e = 0; e < E; ++e)
+        for (int i = 0; i < N; ++i) {
+            int ai = e * N + i;
+            double px = 535.0 + 12.0 * i, py = 360.0 + 4.0 * e;
+            pos[2 * ai] = ppos[2 * ai] = st[2 * ai] = px;
+            pos[2 * ai + 1] = ppos[2 * ai + 1] = st[2 * ai + 1] = py;
+            for (int k = 0; k < W; ++k) {
+                int in = k == near[e];
+                wp[((size_t)ai * W + k) * 2] = in ? px + 3.0 : px + 40.0 + k;
+                wp[((size_t)ai * W + k) * 2 + 1] = in ? py + 3.5 : py - 30.0;
+            }
+            wc[ai] = W;
+            cur[ai] = (int32_t)m0[e];
+            int g = W - 1;
+            while ((m0[e] >> g) & 1u) --g;
+            goal[2 * ai] = wp[((size_t)ai * W + g) * 2];
+            goal[2 * ai + 1] = wp[((size_t)ai * W + g) * 2 + 1];
+        }
+    int bad = 0;
+    for (int t = 0; t < 3; ++t) oc_step(&cfg, &s, act, &out);
+    for (int e = 0; e < E; ++e)
+        for (int i = 0; i < N; ++i) {
+            int ai = e * N + i;
+            bad += (uint32_t)cur[ai] != want[e];
+            bad += goal[2 * ai] != wp[((size_t)ai * W + last[e]) * 2];
+            bad += ((mask[ai] >> 4) & 1) != 0;      /* the third step finds nothing in reach */
+        }
+    free(pos); free(vel); free(ppos); free(pvel); free(goal); free(wp); free(st); free(cur); free(wc); free(wall);
+    free(stp); free(midx); free(reach); free(own); free(radar); free(nei); free(rew); free(act); free(done);
+    free(mask); free(edone); free(bbc);
+    return bad;
+}
+
 int main(void) {
     enum { GW = 23, GH = 13, P = 2048, W = 32 };
     const double bound[4] = {455.0, 680.0, 255.0, 385.0};
@@ -74,6 +131,11 @@ int main(void) {
             free(radar); free(nei); free(rew); free(act); free(done); free(mask); free(edone); free(bbc);
             free(tcpa); free(dcpa); free(cc); free(cp);
         }
+    /* the WGRU oracle's removal mask: bit 31 with cnt = 32, and W = 4 */
+    for (int w = 4; w <= 32; w += 28) {
+        int bad = wgru_mask_edge(occ, bound, w);
+        if (bad) { fprintf(stderr, "wgru mask edge W=%d: %d mismatches\n", w, bad); return 4; }
+    }
     /* the exact threshold fallbacks: goals on the apothem, circles on cell edges, capsules on the bound */
     init_tables();
     int hits = 0;
