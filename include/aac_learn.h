@@ -38,7 +38,17 @@ int aac_attn_bwd(const float *q, const float *k, const float *v, int32_t kv_stri
 
 /* One transition = one ring row made of n_fields consecutive fields; field f has widths[f]
  * elements per transition, source srcs[f] ([E][widths[f]]), dtype[f] 0 = fp32, 1 = uint8.
- * meta (device int64[2]) = {next write position, current size}; updated on the device. */
+ * meta (device int64[2]) = {next write position, current size}; updated on the device.
+ * Contract of the two push entry points (tests/test_replay_ring_gpu.py holds both to it):
+ *   aac_replay_push     reads the position from meta on the device (a second one-thread launch
+ *                       advances it); writes the sum(widths) data columns of each pushed row and
+ *                       nothing else: with row_width > sum(widths) the row tail keeps what the ring
+ *                       held (DeviceReplay allocates the ring zeroed).  No alignment requirement.
+ *   aac_replay_push_at  takes [pos, size] from the caller and stores the advanced pair to meta in
+ *                       the same launch; writes whole rows: the tail row_width - sum(widths) of every
+ *                       pushed row becomes +0.0.  ring must be 16-B aligned; row_width % 4 == 0 takes
+ *                       16-B stores, any other width 4-B stores (the same rows either way).
+ * Both convert uint8 fields to float, need 1 <= E <= capacity, and leave rows they do not push alone. */
 int aac_replay_push(float *ring, int32_t row_width, int64_t capacity, int64_t *meta, int32_t n_fields,
                     const void *const *srcs, const int32_t *widths, const int32_t *dtypes, int32_t E, void *stream);
 /* The same push with the ring position and size known to the caller (pushes are host-initiated,

@@ -6,6 +6,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import learner_ref
+from tests import noise_ref
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -86,11 +87,7 @@ def test_replay_push_gather_sample(native_lib):
     assert torch.equal(first, rep.batch_buffers(512)[0])
 
 
-def _mix64(x):
-    x = x + np.uint64(0x9E3779B97F4A7C15)
-    x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-    x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-    return x ^ (x >> np.uint64(31))
+_mix64 = noise_ref.mix64
 
 
 def _draw_rounds(seed, ctr, block, B, size):
@@ -231,25 +228,16 @@ def test_noise_rows_match_restatement(native_lib):
     ctr = torch.zeros(1, dtype=torch.int64, device=DEV)
     noise = torch.empty(E, N, 2, device=DEV)
     rows = np.arange(E * N, dtype=np.uint64)
-    epn = ep.cpu().numpy()[(rows // N).astype(np.int64)].astype(np.float64)
-    ns, ne = float(np.float32(1.0)), float(np.float32(0.05))
-    var = np.where(epn <= eps_end, ns + (ne - ns) / (eps_end - 1) * (epn - 1), ne)
-    with np.errstate(over="ignore"):
-        for k in range(3):
-            act = torch.rand(E, N, 2, device=DEV, generator=g) * 2 - 1
-            a0 = act.cpu().numpy().reshape(-1, 2)
-            ops.noise_clamp(act, ep, eps_end, 1.0, seed, ctr, noise, noise_end=0.05)
-            assert int(ctr.item()) == k + 1
-            h1 = _mix64(_mix64(_mix64(np.uint64(seed)) ^ np.uint64(k)) ^ (np.uint64(2) * rows))
-            h2 = _mix64(h1 ^ np.uint64(0xD1B54A32D192ED03))
-            u1 = ((h1 >> np.uint64(11)).astype(np.float64) + 1.0) * (1.0 / 9007199254740992.0)
-            u2 = (h2 >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
-            rr = np.sqrt(-2.0 * np.log(u1))
-            want = np.stack([rr * np.cos(6.283185307179586 * u2) * var,
-                             rr * np.sin(6.283185307179586 * u2) * var], 1).astype(np.float32)
-            got = noise.cpu().numpy().reshape(-1, 2)
-            np.testing.assert_array_max_ulp(got, want, maxulp=1)
-            np.testing.assert_array_equal(act.cpu().numpy().reshape(-1, 2), np.clip(a0 + got, -1, 1))
+    epn = ep.cpu().numpy()
+    for k in range(3):
+        act = torch.rand(E, N, 2, device=DEV, generator=g) * 2 - 1
+        a0 = act.cpu().numpy().reshape(-1, 2)
+        ops.noise_clamp(act, ep, eps_end, 1.0, seed, ctr, noise, noise_end=0.05)
+        assert int(ctr.item()) == k + 1
+        want = noise_ref.noise32(seed, k, rows, N, epn, eps_end, 1.0, 0.05)
+        got = noise.cpu().numpy().reshape(-1, 2)
+        np.testing.assert_array_max_ulp(got, want, maxulp=1)
+        np.testing.assert_array_equal(act.cpu().numpy().reshape(-1, 2), np.clip(a0 + got, -1, 1))
 
 
 @pytest.mark.parametrize("N,B", [(3, 64), (5, 256)])
