@@ -150,6 +150,14 @@ int aac_env_reset_stamps(unsigned long long *out, int32_t n_wg);
  * is enqueued on `stream` (ordered after the caller's pending resets and its fill of the buffer). */
 int aac_env_use_episode_buffer(aac_env *env, int32_t *episode_dev, void *stream);
 
+/* Reward terms (aac_terms.h): attaches the caller's device buffer double[E][N][AAC_TERMS_W] (16-byte
+ * aligned, kept alive while attached); NULL detaches it.  While attached, aac_env_step and
+ * aac_env_step_tail launch the step kernel's terms form, which stores every agent's row, and the exact
+ * fix-up keeps the rows of the rewards it rewrites.  While detached the launches are the plain ones.
+ * Host-side only (no launch): it takes effect with the next step call; a captured graph keeps the
+ * form it was captured with. */
+int aac_env_set_terms_buffer(aac_env *env, double *terms_dev);
+
 /* Flight recorder (aac_record.h): aac_record with E and the state sources of ``step`` (pos, vel, goal,
  * map_idx and the episode counter, wherever aac_env_use_episode_buffer has put it) filled from the
  * handle's live device pointers at call time; the rest of ``step`` is the caller's.  RESET after

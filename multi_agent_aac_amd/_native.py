@@ -22,6 +22,8 @@ EXPORTS = (
     "aac_stats_last_error", "aac_stats_accumulate", "aac_stats_reduce",
     "aac_record_last_error", "aac_record", "aac_env_record", "aac_uam_record",
     "aac_monitor_last_error", "aac_monitor_vec", "aac_monitor_commit",
+    "aac_env_set_terms_buffer", "aac_terms_last_error", "aac_terms_names", "aac_terms_accumulate", "aac_terms_reduce",
+    "aac_terms_record",
 )
 
 vp = ctypes.c_void_p
@@ -58,6 +60,19 @@ class StatsStep(ctypes.Structure):         # aac_stats_step
     _fields_ = [("reward", vp), ("reward_f64", i32), ("done", vp), ("mask", vp), ("env_done", vp), ("bbc", vp),
                 ("E", i32), ("N", i32), ("episode_length", i32), ("goal_bit", i32), ("return_mode", i32),
                 ("quota", vp), ("step_index", ctypes.c_int64)]
+
+
+class TermsState(ctypes.Structure):        # aac_terms_state (include/aac_terms.h)
+    _fields_ = [("run", vp), ("ep_count", vp), ("slots", vp)]
+
+
+class TermsStep(ctypes.Structure):         # aac_terms_step
+    _fields_ = [("terms", vp), ("env_done", vp), ("E", i32), ("N", i32), ("quota", vp)]
+
+
+class TermsRecord(ctypes.Structure):       # aac_terms_record_args
+    _fields_ = [("env_ids", vp), ("cursor", vp), ("ep_seen", vp), ("sel", vp), ("terms", vp), ("rows", vp),
+                ("T", i32), ("S", i32), ("N", i32), ("E", i32), ("max_episodes", i32), ("phase", i32)]
 
 
 class RecordEpisode(ctypes.Structure):     # aac_record_episode (include/aac_record.h)
@@ -143,6 +158,13 @@ def lib():
         L.aac_monitor_last_error.restype = ctypes.c_char_p
         L.aac_monitor_vec.argtypes = [ctypes.POINTER(MonitorVecJob), i32, i32, vp]
         L.aac_monitor_commit.argtypes = [ctypes.POINTER(MonitorCommitArgs), vp]
+    if hasattr(L, "aac_terms_accumulate") or not os.environ.get("AAC_LIB"):
+        L.aac_env_set_terms_buffer.argtypes = [vp, vp]
+        L.aac_terms_last_error.restype = ctypes.c_char_p
+        L.aac_terms_names.restype = ctypes.c_char_p
+        L.aac_terms_accumulate.argtypes = [ctypes.POINTER(TermsState), ctypes.POINTER(TermsStep), vp]
+        L.aac_terms_reduce.argtypes = [ctypes.POINTER(TermsState), i32, vp, i32, vp]
+        L.aac_terms_record.argtypes = [ctypes.POINTER(TermsRecord), vp]
     for name in EXPORTS:
         if os.environ.get("AAC_LIB") and not hasattr(L, name):
             continue          # an A/B experiment build of an earlier revision

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/aac_env.h"
+#include "../../include/aac_terms.h"
 #include "aac_geom.h"
 #include "aac_wave.h"
 
@@ -75,7 +76,21 @@ struct Args {
     // variant 1 step: agents with a flagged ray, whose reward's near-building penalty (the radar minimum)
     // band_fix_kernel recomputes from the exact radar (the kernel's minimum is the float one)
     struct RewFix *rfix;
+    double *terms;       // [E][N][AAC_TERMS_W] reward terms (aac_env_set_terms_buffer), step_kernel<.., TERMS> only
 };
+
+// one agent's reward-terms row (include/aac_terms.h): 96 B, six 16-B stores straight from registers
+__device__ __attribute__((always_inline)) void store_terms(double *row, double s0, double s1, double s2, double s3,
+                                                           double s4, double s5, double s6, double g8, double g9,
+                                                           double g10, double g11) {
+    double2 *q = reinterpret_cast<double2 *>(row);
+    q[0] = make_double2(s0, s1);
+    q[1] = make_double2(s2, s3);
+    q[2] = make_double2(s4, s5);
+    q[3] = make_double2(s6, 0.0);
+    q[4] = make_double2(g8, g9);
+    q[5] = make_double2(g10, g11);
+}
 
 // a variant-1 agent whose reward band_fix_kernel recomputes: r = rp - nbp(rmin) (kind 1), (rp - nbp) +
 // 0.0 (kind 2, the normal-step branch), rp (kind 0: no penalty term), rmin over the agent's exact rays
@@ -597,9 +612,11 @@ __device__ inline double wgru_nbp(double rmin, double pb) {
 }
 
 // rp, rk: the reward before its penalty term and how the term enters (RewFix)
+// TERMS: the taken branch's terms and the gauges go to the agent's row trow (include/aac_terms.h)
+template <bool TERMS>
 __device__ __attribute__((always_inline)) double wgru_reward(const Args &A, size_t ai, WpView wp, double2 pp, double2 p, double2 v, uint32_t rm,
                               int cnt, double rmin, int goal, int bnd, int building, int &flag, int &done, int &cg,
-                              uint8_t &fl, double2 start, double &rp, int &rk) {
+                              uint8_t &fl, double2 start, double &rp, int &rk, double *trow) {
     const double px = p.x, py = p.y, pb = A.pb;
     int nrem = cnt - __popc(rm & (cnt >= 32 ? 0xffffffffu : ((1u << cnt) - 1u)));
     double smallest = INFINITY;
@@ -653,7 +670,8 @@ __device__ __attribute__((always_inline)) double wgru_reward(const Args &A, size
                 break;
             }
     }
-    const double dtg = 1 * (npnorm(pp.x - nx.x, pp.y - nx.y) - npnorm(px - nx.x, py - nx.y));
+    const double dafter = npnorm(px - nx.x, py - nx.y);
+    const double dtg = 1 * (npnorm(pp.x - nx.x, pp.y - nx.y) - dafter);
     ASTAMP(6);
     // cross_track_error (WGRU/env:2621-2632): nearest point of the first segment at the smallest
     // pointToSegment distance, then the point distance to it.  A segment whose bounding box lies
@@ -710,19 +728,23 @@ __device__ __attribute__((always_inline)) double wgru_reward(const Args &A, size
         rk = 1;
         done = 1;
         fl |= 8;
+        if constexpr (TERMS) store_terms(trow, -5.0, 0.0, dref, dtg, -ssp, -nbp, 0.0, cross, sp, dafter, rmin);
     } else if (building) {
         done = 1;
         fl |= 16;
         rp = ((((0.0 + dref) - 5) + dtg) - ssp) + 0.0;
         r = rp - nbp;
         rk = 1;
+        if constexpr (TERMS) store_terms(trow, -5.0, 0.0, dref, dtg, -ssp, -nbp, 0.0, cross, sp, dafter, rmin);
     } else if (goal) {
         cg = 1;
         r = rp = (0.0 + 5) + 0.0;
         rk = 0;
+        if constexpr (TERMS) store_terms(trow, 5.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, cross, sp, dafter, rmin);
     } else {
         r = 0.0;
         if (flag && nrem > 1) r = r + 3;
+        if constexpr (TERMS) store_terms(trow, 0.0, r, dref, dtg, -ssp, -nbp, 0.0, cross, sp, dafter, rmin);
         rp = (((r + dref) + dtg) - ssp) + 0.0;
         r = (rp - nbp) + 0.0;
         rk = 2;
@@ -1128,6 +1150,7 @@ struct FixArgs {
     const RewFix *rfix;        // variant 1 step: rewards whose radar minimum is recomputed exactly
     float *reward;
     int rcol;                  // the ring's reward column (RewFix.row >= 0)
+    double *terms;             // attached reward-terms rows (null: none): slots 5 and 11 follow the exact minimum
 };
 
 // The flagged rays of the launch before it (one workgroup; nothing to do in the common case), then the
@@ -1159,6 +1182,11 @@ __device__ __attribute__((always_inline)) void band_fix_body(const FixArgs &F) {
         const double rew = x.kind == 0 ? x.rp : (x.kind == 1 ? x.rp - nbp : (x.rp - nbp) + 0.0);
         F.reward[(size_t)x.e * F.N + x.i] = (float)rew;
         if (F.ring && x.row >= 0) F.ring[x.row * F.rw + F.rcol + x.i] = (float)rew;
+        if (F.terms) {      // the sum of the row's slots stays the rewritten reward
+            double *tr = F.terms + ((size_t)x.e * F.N + x.i) * AAC_TERMS_W;
+            tr[5] = x.kind == 0 ? 0.0 : -nbp;
+            tr[11] = rmin;
+        }
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -1175,7 +1203,7 @@ __device__ __attribute__((always_inline)) void band_fix_body(const FixArgs &F) {
 
 __global__ void __launch_bounds__(256) band_fix_kernel(FixArgs F) { band_fix_body(F); }
 
-template <int VAR, int RM, bool TAIL>
+template <int VAR, int RM, bool TAIL, bool TERMS>
 __global__ void __launch_bounds__(BLOCK, AAC_ENV_MIN_WAVES) step_kernel(Args Ain, const float2 *__restrict__ act,
                                                                          ResetArgs R, Tail T) {
     Args A = Ain;
@@ -1387,9 +1415,9 @@ __global__ void __launch_bounds__(BLOCK, AAC_ENV_MIN_WAVES) step_kernel(Args Ain
             const bool fixr = (S.flags[t] & 0x80) != 0;      // read before the flags are rewritten below
             double rp;
             int rk;
-            r = wgru_reward(A, ai, wv, pp, np, S.vel[t], (uint32_t)cur, wcnt,
-                            __longlong_as_double((long long)S.rmin[t]), goal, bnd, building, wpf, done, cg, fl, st0,
-                            rp, rk);
+            r = wgru_reward<TERMS>(A, ai, wv, pp, np, S.vel[t], (uint32_t)cur, wcnt,
+                                   __longlong_as_double((long long)S.rmin[t]), goal, bnd, building, wpf, done, cg, fl,
+                                   st0, rp, rk, TERMS ? A.terms + ai * AAC_TERMS_W : nullptr);
             if (cg) {
                 reach = 1;
                 A.reach[ai] = 1;
@@ -1431,6 +1459,13 @@ __global__ void __launch_bounds__(BLOCK, AAC_ENV_MIN_WAVES) step_kernel(Args Ain
                     A.wp0[ai] = A.wp[ai * A.W + cur + 1];
                 }
                 r = dtg - pen;
+            }
+            if constexpr (TERMS) {      // the taken branch's terms (include/aac_terms.h), gauges 9 and 10
+                const double2 v = S.vel[t];
+                const bool crash = bnd || ncoll > 0, normal = !crash && !goal;
+                store_terms(A.terms + ai * AAC_TERMS_W, crash ? -20.0 : (goal ? 20.0 : 0.0), 0.0, 0.0,
+                            normal ? dtg : 0.0, 0.0, 0.0, (!bnd && ncoll > 0) || normal ? -pen : 0.0, 0.0,
+                            npnorm(v.x, v.y), after, 0.0);
             }
         }
         uint8_t m = (uint8_t)(bnd | ((ncoll > 0) << 1) | (goal << 2) | (building << 3) | (wpf << 4));
@@ -1611,6 +1646,7 @@ struct aac_env {
     double2 *band_pos;
     int32_t *band_cnt;
     RewFix *rfix;             // variant 1: rewards recomputed from the exact radar minimum
+    double *terms;            // caller's reward-terms buffer (aac_env_set_terms_buffer), null: detached
 };
 
 constexpr int BAND_CAP = 16384;   // flagged rays per launch: never more than a few in practice; the
@@ -1682,6 +1718,7 @@ static Args make_args(const aac_env *h, const aac_step_out *o) {
     A.band_cnt = h->band_cnt;
     A.band_cap = BAND_CAP;
     A.rfix = c.variant ? h->rfix : nullptr;
+    A.terms = h->terms;
     return A;
 }
 
@@ -1712,6 +1749,7 @@ static FixArgs fix_args(const aac_env *h, const Args &A, const uint8_t *env_done
     F.rfix = A.rfix;
     F.reward = A.reward;
     F.rcol = rcol;
+    F.terms = nullptr;      // step launches with an attached buffer set it (reset launches never write terms)
     return F;
 }
 
@@ -1850,10 +1888,17 @@ static int launch_step(aac_env *h, const float *actions, const aac_step_out *o, 
     const float2 *a2 = reinterpret_cast<const float2 *>(actions);
     FixArgs F = tail ? fix_args(h, A, T.reset ? o->env_done : nullptr, T.ring, T.rw, T.late[LATE_RADAR], T.late[LATE_REW])
                      : fix_args(h, A);
+    F.terms = A.variant ? A.terms : nullptr;
+    const bool terms = A.terms != nullptr;
 #define STEP_LAUNCH(V, M)                                                                                        \
     do {                                                                                                         \
-        if (tail) hipLaunchKernelGGL((step_kernel<V, M, true>), grid, block, lds, st, A, a2, R, T);              \
-        else hipLaunchKernelGGL((step_kernel<V, M, false>), grid, block, lds, st, A, a2, R, T);                  \
+        if (terms) {                                                                                             \
+            if (tail) hipLaunchKernelGGL((step_kernel<V, M, true, true>), grid, block, lds, st, A, a2, R, T);    \
+            else hipLaunchKernelGGL((step_kernel<V, M, false, true>), grid, block, lds, st, A, a2, R, T);        \
+        } else {                                                                                                 \
+            if (tail) hipLaunchKernelGGL((step_kernel<V, M, true, false>), grid, block, lds, st, A, a2, R, T);   \
+            else hipLaunchKernelGGL((step_kernel<V, M, false, false>), grid, block, lds, st, A, a2, R, T);       \
+        }                                                                                                        \
     } while (0)
     if (A.variant) STEP_LAUNCH(1, AAC_RADAR_OBSTACLES);
     else if (A.radar_mode == AAC_RADAR_DRONES) STEP_LAUNCH(0, AAC_RADAR_DRONES);
@@ -2089,6 +2134,14 @@ int aac_env_use_episode_buffer(aac_env *h, int32_t *episode_dev, void *stream) {
         HIPCHK(hipMemcpyAsync(episode_dev, h->episode, sizeof(int32_t) * (size_t)h->cfg.E, hipMemcpyDeviceToDevice,
                               (hipStream_t)stream));
     h->episode = episode_dev;
+    return AAC_OK;
+}
+
+int aac_env_set_terms_buffer(aac_env *h, double *terms_dev) {
+    if (!h) return fail(AAC_E_INVALID, "null handle");
+    if (reinterpret_cast<uintptr_t>(terms_dev) & 15)
+        return fail(AAC_E_INVALID, "set_terms_buffer: the buffer must be 16-byte aligned (rows are stored as double2)");
+    h->terms = terms_dev;
     return AAC_OK;
 }
 

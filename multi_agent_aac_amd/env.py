@@ -111,6 +111,7 @@ class BatchedEnv:
             _native.check(_native.lib().aac_env_create(ctypes.byref(cfg), dev_index, ctypes.byref(h)),
                           "aac_env_create")
         self._h = h
+        self.terms = None       # the attached reward-terms buffer (use_terms_buffer)
         self.bufs = self.alloc_buffers()
 
     def __del__(self):
@@ -253,6 +254,23 @@ class BatchedEnv:
         self._episode_buf = episode
         return episode
 
+    def use_terms_buffer(self, t=None, detach=False):
+        """Attach a reward-terms buffer (float64 [E][N][12], include/aac_terms.h): ``t``, or a new one;
+        ``env.terms`` holds it.  From the next step on the step kernels store every agent's reward terms
+        in it (a captured graph keeps the form it was captured with).  ``detach=True`` detaches it:
+        the step launches are the plain ones again."""
+        if detach:
+            t = None
+        else:
+            if t is None:
+                t = torch.zeros(self.E, self.N, 12, dtype=torch.float64, device=self.device)
+            if t.dtype != torch.float64 or tuple(t.shape) != (self.E, self.N, 12) or not t.is_contiguous() \
+                    or t.device != self.device:
+                raise ValueError(f"terms buffer: float64 ({self.E}, {self.N}, 12), contiguous, on {self.device}")
+        _native.check(_native.lib().aac_env_set_terms_buffer(self._h, _ptr(t)), "aac_env_set_terms_buffer")
+        self.terms = t
+        return t
+
     def auto_reset(self, env_done=None, out: Optional[StepBuffers] = None):
         """Redraw OD from the device bank for envs with env_done != 0 (None = all envs)."""
         out = out or self.bufs
@@ -325,10 +343,17 @@ class env_simulator:
     ``world_map`` is the x-major occupancy grid (the reference passes the bounded map built
     from the shapefile, ATT/params:61); ``building_polygons``/``allGridPoly`` are accepted for
     signature compatibility but the geometry is rebuilt from ``world_map`` (10 m cells).
+
+    ``reward_terms=True`` attaches a reward-terms buffer (include/aac_terms.h) and ``ss_reward`` hands
+    out the reference's per-step pieces from it: ``step_reward_record[i] = [dist_to_ref_line,
+    dist_to_goal]`` (ATT/env:2590; the first is 0.0 in this env) and one ``eps_status_holder[i]`` row per
+    step (``display_one_eps_status``, ATT/env:2596-2624).  ``dist_to_goal`` is the progress term as it
+    entered the reward: 0.0 on a step that took the crash or goal branch.  Off (the default):
+    ``[0.0, None]`` and an untouched holder.
     """
 
     def __init__(self, world_map, building_polygons=None, grid_length=10, bound=None, allGridPoly=None,
-                 agentConfig=None, radar_mode="drones", compat=True, seed=None):
+                 agentConfig=None, radar_mode="drones", compat=True, seed=None, reward_terms=False):
         occ = np.asarray(world_map, dtype=np.uint8)
         self.world_map_2D = occ
         self.buildingPolygons = building_polygons
@@ -343,6 +368,7 @@ class env_simulator:
         self.compat = compat
         self._rng = np.random.default_rng(seed)
         self._env = None
+        self.reward_terms = bool(reward_terms)
 
     def create_world(self, total_agentNum, n_actions, gamma, tau, target_update, largest_Nsigma, smallest_Nsigma,
                      ini_Nsigma, max_xy, max_spd, acc_range, full_observable_critic_flag=True):
@@ -360,6 +386,8 @@ class env_simulator:
                                team_reward=True, vmax=float(max_spd), acc_max=float(abs(acc_range[1])),
                                bound=self.bound, cell=float(self.gridlength))
         self._env_agentwise = None
+        if self.reward_terms:
+            self._env.use_terms_buffer()
 
     # ---------------------------------------------------------------- OD (ATT/env:251-347)
     def _draw_od(self, N):
@@ -464,6 +492,8 @@ class env_simulator:
         self._env.step(a)
         b = self._env.bufs
         self._last = {k: getattr(b, k)[0].cpu().numpy() for k in ("reward", "done", "mask", "bbc")}
+        if self.reward_terms:
+            self._last["terms"] = self._env.terms[0].cpu().numpy()
         self._sync_agents()
         state, norm = self._states()
         return state, norm, [], [], [], [], [], []
@@ -483,7 +513,19 @@ class env_simulator:
         for i in range(N):
             if step_collision_record is not None:
                 step_collision_record[i].append([0, 0, 0, int(bool(mask[i] & 8)), 0, 0])
-            if step_reward_record is not None:
+            if self.reward_terms:
+                # slots of include/aac_terms.h: 3 progress, 9 |vel|, 10 distance to goal[-1] after the step
+                t = last["terms"][i]
+                dtg = float(t[3])
+                if step_reward_record is not None:
+                    step_reward_record[i] = [0.0, dtg]
+                if eps_status_holder is not None:
+                    row = [float(t[10]), dtg, 0.0, 0.0, 0.0, 0.0, float(t[9]), 0.0, 0.0]
+                    if eps_status_holder[i] is None:
+                        eps_status_holder[i] = [row]
+                    else:
+                        eps_status_holder[i].append(row)
+            elif step_reward_record is not None:
                 step_reward_record[i] = [0.0, None]
         bbc = [bool(v) for v in last["bbc"]]
         return reward, done, check_goal, step_reward_record, eps_status_holder, step_collision_record, bbc

@@ -23,9 +23,14 @@ POLL = 16      # steps between two reads of the "envs still under quota" word
 
 class Evaluator:
     """``evaluate(k)`` plays k episodes in each of E eval envs and returns their statistics
-    (``EpisodeStats.read()``: exactly E * k episodes)."""
+    (``EpisodeStats.read()``: exactly E * k episodes).
 
-    def __init__(self, trainer, E=None, seed=0, log=0):
+    ``terms=True`` (ATT and GRU trainers): the eval env gets a reward-terms buffer and a reward ledger
+    (``terms.RewardLedger``) fed beside the statistics under the same quota, so it holds the same
+    episode set; ``evaluate`` then returns ``(stats, ledger.read())`` and ``record``
+    ``(stats, Trajectories, ledger.read())``, the trajectories with a ``terms`` array."""
+
+    def __init__(self, trainer, E=None, seed=0, log=0, terms=False):
         self.tr, self.model = trainer, trainer.model
         tenv = trainer.env
         self.E, self.N = int(E or trainer.E), trainer.N
@@ -52,6 +57,10 @@ class Evaluator:
         self.bufs = [self.env.alloc_buffers(), self.env.alloc_buffers()]
         self.stats = EpisodeStats.for_env(self.env, log=log)
         self.quota = torch.zeros(self.E, dtype=torch.int32, device=dev)
+        self.ledger = None
+        if terms:
+            from .terms import RewardLedger
+            self.ledger = RewardLedger.for_env(self.env)      # NotImplementedError for the UAM env
         if self.gru:
             from . import gru
             # hidden states as the trainer's ping-pong pair, and act plans of this object's own: the
@@ -79,6 +88,7 @@ class Evaluator:
             self.env.step(act, out=n)
             self.stats.accumulate(n, quota=self.quota)
             self.env.auto_reset(n.env_done, out=n)
+            return
         elif self.gru:
             act, hn, _ = self._acts[p](None)
             # a new episode starts from a zero hidden state, as in training (WGRU/ma_main:476-478)
@@ -88,6 +98,8 @@ class Evaluator:
             act = self.model.act(c.own, c.radar, c.nei, self.episode, noisy=False)
             self.env.step_tail(act, out=n, replay=None)
             self.stats.accumulate(n, quota=self.quota)
+        if self.ledger is not None:
+            self.ledger.accumulate(n, quota=self.quota)
 
     @torch.no_grad()
     def _record_step(self, p):
@@ -105,6 +117,8 @@ class Evaluator:
         self.env.step(act, out=n)
         self._rec.after_step(n, act)
         self.stats.accumulate(n, quota=self.quota)
+        if self.ledger is not None:
+            self.ledger.accumulate(n, quota=self.quota)
         if hn is not None:
             from . import gru
             gru.reset_hidden(hn, n.env_done)
@@ -134,6 +148,8 @@ class Evaluator:
             self._graphs = self._capture()
         self._start()
         self.stats.reset()
+        if self.ledger is not None:
+            self.ledger.reset()
         self.quota.fill_(k)
         # an episode takes at most episode_length + 1 steps (timeout: episode_length < len)
         most = k * (self.episode_length + 1)
@@ -144,7 +160,7 @@ class Evaluator:
                 self._step(s & 1)
             if (s + 1) % POLL == 0 and self.stats.under_quota() == 0:
                 break
-        return self.stats.read()
+        return self.stats.read() if self.ledger is None else (self.stats.read(), self.ledger.read())
 
     def record(self, episodes_per_env=1, env_ids=None, steps=None):
         """``evaluate(k)`` with a flight recorder on the envs ``env_ids`` (None: all): the same episode
@@ -154,6 +170,8 @@ class Evaluator:
         ``evaluate`` and its graphs are not involved."""
         steps_run = self._record_rollout(episodes_per_env, env_ids, steps)
         assert steps_run > 0
+        if self.ledger is not None:
+            return self.stats.read(), self._rec.read(), self.ledger.read()
         return self.stats.read(), self._rec.read()
 
     def _record_rollout(self, episodes_per_env=1, env_ids=None, steps=None):
@@ -174,6 +192,8 @@ class Evaluator:
             self._rec_graphs = self._capture(self._record_step)
         self._start()
         self.stats.reset()
+        if self.ledger is not None:
+            self.ledger.reset()
         self.quota.fill_(k)
         rec.reset()
         rec.after_reset(None)

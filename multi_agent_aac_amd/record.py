@@ -27,7 +27,7 @@ TRACK_FIELDS = (("cursor", "<i4"), ("ep_seen", "<i4"), ("dropped", "<i4"), ("run
                 ("run_min_t", "<i4"), ("run_flags", "<i4"), ("run_return", "<f8"), ("run_min_sep", "<f8"))
 
 
-def row_fields(N, heading=False, clouds=False):
+def row_fields(N, heading=False, clouds=False, terms=False):
     """name -> (dtype, shape of one row) of the [T][S]-major row arrays."""
     f = {"header": ("<i4", (4,)), "pos": ("<f8", (N, 2)), "vel": ("<f8", (N, 2)), "goal": ("<f8", (N, 2)),
          "act": ("<f4", (N, 2)), "reward": ("<f8", (N,)), "done": ("u1", (N,)), "mask": ("u1", (N,)),
@@ -36,6 +36,8 @@ def row_fields(N, heading=False, clouds=False):
         f["heading"] = ("<f8", (N,))
     if clouds:
         f["clouds"] = ("<f8", (2, 2))
+    if terms:
+        f["terms"] = ("<f8", (N, 12))       # the reward terms of the step (include/aac_terms.h); zeros in a reset row
     return f
 
 
@@ -62,6 +64,12 @@ class Trajectories:
             assert k in self.rows and self.rows[k].shape[0] == T, k
         self.S = self.rows["header"].shape[1]
         self.N = self.rows["pos"].shape[2]
+
+    @property
+    def terms(self):
+        """[T][S][N][12] reward terms of every recorded step (``terms.names()``; the left-to-right sum of
+        slots 0..7 is the agent's own reward), or None when the env had no terms buffer."""
+        return self.rows.get("terms")
 
     def episodes(self, track=None):
         """A list of dicts, one per finished episode: the summary fields (``ret``, ``min_sep``,
@@ -145,19 +153,25 @@ class FlightRecorder:
         self.env_ids = torch.as_tensor(ids, device=d)
         tt = {"<i4": torch.int32, "<f8": torch.float64, "<f4": torch.float32, "u1": torch.uint8}
         self.track = {k: torch.zeros(self.T, dtype=tt[dt], device=d) for k, dt in TRACK_FIELDS}
+        # an env with a reward-terms buffer (BatchedEnv.use_terms_buffer) attached when the recorder is
+        # built: its rows are recorded too
+        self.terms_src = None if self.uam else getattr(env, "terms", None)
         self.rows = {k: torch.zeros(self.T, self.S, *shp, dtype=tt[dt], device=d)
-                     for k, (dt, shp) in row_fields(N, heading=self.uam, clouds=self.uam).items()}
+                     for k, (dt, shp) in row_fields(N, heading=self.uam, clouds=self.uam,
+                                                    terms=self.terms_src is not None).items()}
         self.summaries = torch.zeros(self.T, self.P, EPISODE.itemsize, dtype=torch.uint8, device=d)
         st = _native.RecordState()
         st.env_ids, st.T, st.S, st.P, st.N = self.env_ids.data_ptr(), self.T, self.S, self.P, N
         for k, t in list(self.track.items()) + list(self.rows.items()):
-            setattr(st, k, t.data_ptr())
+            if k != "terms":
+                setattr(st, k, t.data_ptr())
         st.episodes = self.summaries.data_ptr()
         self._st, self._st_ref = st, ctypes.byref(st)
         L = _native.lib()
         self._call = L.aac_uam_record if self.uam else L.aac_env_record
         self._err = L.aac_uam_last_error if self.uam else L.aac_last_error
         self._steps = {}        # (id(bufs), actions pointer) or ("reset", sel pointer) -> RecordStep
+        self._tsteps = {}       # phase, sel pointer -> TermsRecord (the terms rows' own launch)
         self._torch, self._native = torch, _native
         self.reset()
 
@@ -174,6 +188,23 @@ class FlightRecorder:
         for t in self.track.values():
             t.zero_()
         self.track["run_min_sep"].fill_(math.inf)
+
+    def _launch_terms(self, phase, sel=None):
+        """The terms rows of this step / reset, before the record launch advances the cursors."""
+        key = (phase, None if sel is None else sel.data_ptr())
+        hit = self._tsteps.get(key)
+        if hit is None or hit[0] is not sel:
+            a = self._native.TermsRecord()
+            a.env_ids, a.cursor, a.ep_seen = (self.env_ids.data_ptr(), self.track["cursor"].data_ptr(),
+                                              self.track["ep_seen"].data_ptr())
+            a.sel = None if sel is None else sel.data_ptr()
+            a.terms, a.rows = self.terms_src.data_ptr(), self.rows["terms"].data_ptr()
+            a.T, a.S, a.N, a.E, a.max_episodes, a.phase = self.T, self.S, self.N, self.E, self.P, phase
+            hit = self._tsteps[key] = (sel, ctypes.byref(a), a)
+        L = self._native.lib()
+        rc = L.aac_terms_record(hit[1], self._torch.cuda.current_stream().cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"aac_terms_record failed ({rc}): {L.aac_terms_last_error().decode(errors='replace')}")
 
     def _launch(self, hit):
         rc = self._call(self.env._h, self._st_ref, hit[1], self._torch.cuda.current_stream().cuda_stream)
@@ -201,6 +232,8 @@ class FlightRecorder:
         def fill(p):
             p.phase = PHASE_RESET
             p.sel = None if sel is None else sel.data_ptr()
+        if self.terms_src is not None:
+            self._launch_terms(PHASE_RESET, sel)
         self._launch(self._cached(("reset", None if sel is None else sel.data_ptr()), (sel,), fill))
 
     def after_step(self, bufs, actions):
@@ -225,6 +258,8 @@ class FlightRecorder:
             p.act, p.act_f64 = a.data_ptr(), int(a.dtype == torch.float64)
             p.reward, p.reward_f64 = r.data_ptr(), int(r.dtype == torch.float64)
             p.done, p.mask, p.env_done = bufs.done.data_ptr(), bufs.mask.data_ptr(), bufs.env_done.data_ptr()
+        if self.terms_src is not None:
+            self._launch_terms(PHASE_STEP)
         self._launch(self._cached((id(bufs), actions.data_ptr()), (bufs, actions), fill))
 
     def read(self):

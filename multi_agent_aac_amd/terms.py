@@ -1,0 +1,146 @@
+"""Reward ledger (include/aac_terms.h): which terms an episode's return is made of, kept on the device.
+
+With a terms buffer attached (``BatchedEnv.use_terms_buffer``) the env step kernels store one row of
+``WIDTH`` doubles per (env, agent): the eight contribution slots ``CONTRIB`` -- what the taken reward
+branch added, sign included; their left-to-right sum is the agent's own reward -- and four gauges.
+``RewardLedger.accumulate(bufs)`` is one small launch after each env step on torch's current stream (it
+may be captured in a HIP graph with the step) and keeps, per finished episode, the sum of every
+contribution slot over the episode's steps and agents; ``read()`` folds the per-workgroup slots and
+downloads count, mean, std, min, max and each slot's share of the mean return.
+
+Scope: the ATT and WGRU variants of ``BatchedEnv``.  The UAM and MPE envs emit no terms; with several
+ranks each rank keeps its own ledger; a checkpoint does not carry the ledger (a resumed run starts an
+empty one).
+"""
+import ctypes
+import math
+
+import numpy as np
+import torch
+
+from . import _native
+
+EPW = 256             # AAC_STATS_EPW: envs per workgroup (= per slot)
+WIDTH = 12            # AAC_TERMS_W
+SLOTS = 8             # AAC_TERMS_SLOTS
+FIELDS = 33           # AAC_TERMS_FIELDS: episodes, then sum / sqsum / min / max of the 8 slots
+F_SUM, F_SQ, F_MIN, F_MAX = 1, 1 + SLOTS, 1 + 2 * SLOTS, 1 + 3 * SLOTS
+_names = None
+
+
+def names():
+    """The ``WIDTH`` slot names in row order: the header's table (AAC_TERMS_NAMES), read from the library."""
+    global _names
+    if _names is None:
+        _names = tuple(_native.lib().aac_terms_names().decode().split(","))
+        assert len(_names) == WIDTH
+    return _names
+
+
+def _chk(rc, what):
+    if rc != 0:
+        msg = _native.lib().aac_terms_last_error().decode(errors="replace")
+        raise RuntimeError(f"{what} failed ({rc}): {msg}")
+
+
+def _stream():
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+class RewardLedger:
+    """Per-episode totals of the reward terms of E envs x N agents."""
+
+    def __init__(self, env):
+        self.env, self.E, self.N = env, env.E, env.N
+        d = self.device = env.device
+        E, G = self.E, (self.E + EPW - 1) // EPW
+        self.run = torch.zeros(E, self.N, SLOTS, dtype=torch.float64, device=d)
+        self.ep_count = torch.zeros(E, dtype=torch.int32, device=d)
+        self.slots = torch.zeros(G, FIELDS, dtype=torch.int64, device=d)
+        self.totals = torch.zeros(FIELDS, dtype=torch.int64, device=d)
+        self.quota = torch.zeros(E, dtype=torch.int32, device=d)      # used by accumulate(quota=<int>)
+        st = _native.TermsState()
+        st.run, st.ep_count, st.slots = self.run.data_ptr(), self.ep_count.data_ptr(), self.slots.data_ptr()
+        self._st, self._st_ref = st, ctypes.byref(st)
+        self._accumulate = _native.lib().aac_terms_accumulate
+        self._steps = {}        # id(bufs), quota pointer, terms pointer -> TermsStep
+        self.reset()
+
+    @classmethod
+    def for_env(cls, env):
+        """For a ``BatchedEnv`` (att or wgru).  The env's terms buffer is attached if it has none."""
+        from .env import BatchedEnv
+        if not isinstance(env, BatchedEnv):
+            raise NotImplementedError(f"RewardLedger: {type(env).__name__} emits no reward terms; the ledger covers "
+                                      "the ATT and WGRU variants of BatchedEnv (not the UAM or MPE envs)")
+        if env.terms is None:
+            env.use_terms_buffer()
+        return cls(env)
+
+    def reset(self):
+        """Empty totals, running sums and episode counts."""
+        for t in (self.run, self.ep_count, self.slots):
+            t.zero_()
+        sd = self.slots.view(torch.float64)
+        sd[:, F_MIN:F_MAX] = math.inf
+        sd[:, F_MAX:] = -math.inf
+
+    def accumulate(self, bufs, quota=None):
+        """Add the step whose outputs are in ``bufs`` (``StepBuffers``; its ``env_done`` is read) and
+        whose terms are in the env's attached buffer, after the step launch on the same stream.
+        ``quota``: int32 [E] tensor (or an int, kept in ``self.quota``), the rule of
+        ``EpisodeStats.accumulate``: an env with that many finished episodes contributes nothing more."""
+        if isinstance(quota, int):
+            self.quota.fill_(quota)
+            quota = self.quota
+        terms = self.env.terms
+        if terms is None:
+            raise RuntimeError("RewardLedger.accumulate: the env has no terms buffer attached (use_terms_buffer)")
+        key = (id(bufs), None if quota is None else quota.data_ptr(), terms.data_ptr())
+        hit = self._steps.get(key)
+        if hit is None or hit[0] is not bufs:
+            t = bufs.env_done
+            if t.dtype != torch.uint8 or tuple(t.shape) != (self.E,) or not t.is_contiguous():
+                raise ValueError(f"env_done {tuple(t.shape)} {t.dtype}: expected ({self.E},) uint8")
+            if quota is not None and (quota.dtype != torch.int32 or tuple(quota.shape) != (self.E,)
+                                      or not quota.is_contiguous()):
+                raise ValueError("quota: int32 [E]")
+            p = _native.TermsStep()
+            p.terms, p.env_done, p.E, p.N = terms.data_ptr(), t.data_ptr(), self.E, self.N
+            p.quota = None if quota is None else quota.data_ptr()
+            if len(self._steps) > 64:
+                self._steps.clear()
+            hit = self._steps[key] = (bufs, ctypes.byref(p), quota, p, terms)
+        rc = self._accumulate(self._st_ref, hit[1], torch.cuda.current_stream().cuda_stream)
+        if rc != 0:
+            _chk(rc, "aac_terms_accumulate")
+
+    def raw(self, clear=False):
+        """The folded totals record as int64 [FIELDS] (view as float64 for the sums); synchronises."""
+        _chk(_native.lib().aac_terms_reduce(self._st_ref, self.E, ctypes.c_void_p(self.totals.data_ptr()),
+                                            int(bool(clear)), _stream()), "aac_terms_reduce")
+        return self.totals.cpu().numpy()
+
+    def read(self, clear=False):
+        """``{"episodes": n, "return_mean": sum of the slot means, "terms": {name: {"mean", "std", "min",
+        "max", "sum", "share"}}}`` over the finished episodes (synchronises); a term's ``share`` is its
+        mean over ``return_mean``.  ``clear`` empties the totals afterwards; running episodes carry on."""
+        return summarize(self.raw(clear))
+
+
+def summarize(raw):
+    """``RewardLedger.read()`` from a totals record (int64 [FIELDS])."""
+    raw = np.ascontiguousarray(raw, dtype=np.int64)
+    d = raw.view(np.float64)
+    n = int(raw[0])
+    nm = names()[:SLOTS]
+    mean = [float(d[F_SUM + k]) / n if n else math.nan for k in range(SLOTS)]
+    total = math.fsum(mean) if n else math.nan
+    out = {"episodes": n, "return_mean": total, "terms": {}}
+    for k, name in enumerate(nm):
+        out["terms"][name] = {
+            "sum": float(d[F_SUM + k]), "mean": mean[k],
+            "std": math.sqrt(max(float(d[F_SQ + k]) / n - mean[k] * mean[k], 0.0)) if n else math.nan,
+            "min": float(d[F_MIN + k]) if n else math.nan, "max": float(d[F_MAX + k]) if n else math.nan,
+            "share": mean[k] / total if n and total != 0.0 else math.nan}
+    return out

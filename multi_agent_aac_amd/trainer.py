@@ -112,12 +112,22 @@ class CheckpointMixin:
         """End of a run: checks that no launch overflowed the env's exact threshold fix-up list
         (``env.check_band_capacity``, where the env has one), that the learner monitor (if any) saw no
         non-finite update (``monitor.check()``: FloatingPointError naming the update), and returns the
-        episode statistics (``stats.read()``; None without ``stats=True``).  Synchronises."""
+        episode statistics (``stats.read()``; None without ``stats=True``), with the reward ledger's report
+        under ``"terms"`` where the trainer keeps one.  Synchronises."""
         if hasattr(self.env, "check_band_capacity"):
             self.env.check_band_capacity()
         if getattr(self, "monitor", None) is not None:
             self.monitor.check()
-        return self.stats.read() if self.stats is not None else None
+        out = self.stats.read() if self.stats is not None else None
+        if getattr(self, "ledger", None) is not None:      # with a ledger: the statistics plus its report
+            out = dict(out or {}, terms=self.ledger.read())
+        return out
+
+    def terms(self):
+        """The reward ledger's report (``terms.RewardLedger.read()``; None without ``terms=True``).
+        Synchronises."""
+        led = getattr(self, "ledger", None)
+        return led.read() if led is not None else None
 
 
 class Trainer(CheckpointMixin):
@@ -136,9 +146,17 @@ class Trainer(CheckpointMixin):
     ``self.monitor`` (``monitor.LearnerMonitor``), fed by launches inside every update, eager or
     captured; ``finish()`` raises FloatingPointError if an update went non-finite.  Off (the default)
     the launch lists are unchanged and ``self.monitor`` is None.  Its tensors are checkpointed as
-    ``monitor.*`` under the same rules as ``stats.*``."""
+    ``monitor.*`` under the same rules as ``stats.*``.
 
-    def __init__(self, E, N, B, memory, radar, seed, pg=None, model="att", maps=1, stats=False, monitor=False):
+    ``terms=True`` attaches a reward-terms buffer to the env (its step launches then store every agent's
+    reward terms) and keeps the per-episode totals of the terms in ``self.ledger``
+    (``terms.RewardLedger``): one small launch after the stats launch position of every env step, eager
+    or inside the whole-step graphs; ``terms()`` reads them.  Off (the default) the env launches and the
+    launch sequence are unchanged and ``self.ledger`` is None.  The ledger is not checkpointed: a
+    resumed run starts an empty one."""
+
+    def __init__(self, E, N, B, memory, radar, seed, pg=None, model="att", maps=1, stats=False, monitor=False,
+                 terms=False):
         from . import world
         from .env import BatchedEnv
         from .maddpg import MADDPG
@@ -187,6 +205,10 @@ class Trainer(CheckpointMixin):
         self.pre_step_hooks, self.post_step_hooks = [], []
         self._init_stats(stats)
         self._init_monitor(monitor, N, torch.float32)
+        self.ledger = None
+        if terms:       # the env's step launches take their terms form from here on (no graph exists yet)
+            from .terms import RewardLedger
+            self.ledger = RewardLedger.for_env(self.env)
 
     def graph_ok(self):
         """Whole-step graphs: the fused env tail, one rank, the fused learner (ATT: AAC_STEP_GRAPH; the
@@ -214,6 +236,8 @@ class Trainer(CheckpointMixin):
                                pos_io=(self.pos_dev[p], self.pos_dev[1 - p]))
             if self.stats is not None:
                 self.stats.accumulate(n)
+            if self.ledger is not None:
+                self.ledger.accumulate(n)
             self.model._plan(self.B).run()
             return
         act = self.model.act(c.own, c.radar, c.nei, self.episode, noisy=True)
@@ -221,6 +245,8 @@ class Trainer(CheckpointMixin):
         self.env.step_tail(act, out=n, replay=self.replay, srcs=srcs, pos_io=(self.pos_dev[p], self.pos_dev[1 - p]))
         if self.stats is not None:
             self.stats.accumulate(n)
+        if self.ledger is not None:
+            self.ledger.accumulate(n)
         self.model._fused_plan(self.B).run_streams(side)
 
     def _capture_step(self, p, steps=1):
@@ -332,6 +358,8 @@ class Trainer(CheckpointMixin):
                     self.env.step_tail(act, out=n, replay=self.replay, srcs=srcs)
                 if self.stats is not None:
                     self.stats.accumulate(n)
+                if self.ledger is not None:
+                    self.ledger.accumulate(n)
             if time_env:
                 ev1.record()
                 self.env_events.append((ev0, ev1))
@@ -346,6 +374,8 @@ class Trainer(CheckpointMixin):
             self.env.step(act, out=n)
             if self.stats is not None:
                 self.stats.accumulate(n)
+            if self.ledger is not None:
+                self.ledger.accumulate(n)
         if time_env:
             ev1.record()
             self.env_events.append((ev0, ev1))
