@@ -24,6 +24,7 @@
 
 #include "../../include/aac_fused.h"
 #include "aac_wave.h"
+#include "aac_adam_bc.h"
 
 namespace {
 
@@ -799,8 +800,8 @@ __global__ void __launch_bounds__(256, 5) gemm_kernel(GBatch g) {
 // sum of the ns split-K partial copies of element i, in copy order (so the result does not depend
 // on how the loads are batched): eight independent loads in flight per step instead of a
 // dependent chain of ns
-__device__ __forceinline__ float sum_copies(const float *__restrict__ gpart, int ns, int64_t n, int64_t i) {
-    float gi = gpart[i];
+// (gi: copy 0's value, which a caller may have loaded earlier)
+__device__ __forceinline__ float sum_copies(const float *__restrict__ gpart, int ns, int64_t n, int64_t i, float gi) {
     int s = 1;
     for (; s + 8 <= ns; s += 8) {
         float v[8];
@@ -813,25 +814,39 @@ __device__ __forceinline__ float sum_copies(const float *__restrict__ gpart, int
     return gi;
 }
 
+__device__ __forceinline__ float sum_copies(const float *__restrict__ gpart, int ns, int64_t n, int64_t i) {
+    return sum_copies(gpart, ns, n, i, gpart[i]);
+}
+
 __global__ void adam_sum_kernel(float *p, const float *__restrict__ gpart, int ns, int64_t gs, float *gout, float *m,
                                 float *v, int64_t n, float lr, float b1, float b2, float eps, const int32_t *step, int step_add) {
+    __shared__ float bc[2];
     const int t = *step + step_add;
-    const double bc1 = 1.0 - pow((double)b1, (double)t);
-    const double bc2 = 1.0 - pow((double)b2, (double)t);
-    const float step_size = (float)((double)lr / bc1);
-    const float bc2s = (float)sqrt(bc2);
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    // the first trip's loads go out ahead of the bias corrections (clamped index, unconditional: a
+    // thread past n still reaches the barrier in adam_bias_bcast)
+    const int64_t ic = i < n ? i : n - 1;
+    float m0 = m[ic], v0 = v[ic], p0 = p[ic];
+    const float g0 = gpart[ic];
+    float step_size, bc2s;
+    adam_bias_bcast(bc, lr, b1, b2, t, step_size, bc2s);
+    float gi = sum_copies(gpart, ns, gs, ic, g0);
     const float w1 = (float)(1.0 - (double)b1), w2 = (float)(1.0 - (double)b2);
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float gi = sum_copies(gpart, ns, gs, i);
+    while (i < n) {
         if (gout) gout[i] = gi;
-        float mi = m[i];
+        float mi = m0;
         mi = mi + w1 * (gi - mi);               // exp_avg.lerp_(grad, 1 - beta1)
-        float vi = v[i] * b2;                   // exp_avg_sq.mul_(beta2)
+        float vi = v0 * b2;                     // exp_avg_sq.mul_(beta2)
         vi = vi + w2 * (gi * gi);               //   .addcmul_(grad, grad, 1 - beta2)
         const float den = sqrtf(vi) / bc2s + eps;
-        p[i] = p[i] + (-step_size) * (mi / den);   // param.addcdiv_(exp_avg, denom, -step_size)
+        p[i] = p0 + (-step_size) * (mi / den);     // param.addcdiv_(exp_avg, denom, -step_size)
         m[i] = mi;
         v[i] = vi;
+        i += stride;
+        if (i >= n) break;
+        m0 = m[i], v0 = v[i], p0 = p[i];
+        gi = sum_copies(gpart, ns, gs, i);
     }
 }
 
@@ -846,17 +861,23 @@ __global__ void adam_sum_kernel(float *p, const float *__restrict__ gpart, int n
 // the four-group copy sum of adam_sum4_kernel / sum_partials4_kernel (one order for both, so a
 // world > 1 update -- sum, all-reduce, Adam on the sum x 1 / world -- is bit-equal to one rank's fused
 // step on identical data when world is a power of two)
-__device__ __forceinline__ f4 copy_sum4(const float *__restrict__ gpart, int ns, int64_t gs, int64_t ii, int g) {
+// the eight loads of copies s0, s0 + 4, .. s0 + 28 (clamped copy index, unconditional: selected when
+// they are summed -- a select around each load would make the compiler branch and drain per load)
+__device__ __forceinline__ void copy_load8(const float *__restrict__ gpart, int ns, int64_t gs, int64_t ii, int s0,
+                                           f4 (&x)[8]) {
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        const int sc = s0 + 4 * u;
+        x[u] = *reinterpret_cast<const f4 *>(gpart + (int64_t)(sc < ns ? sc : 0) * gs + ii);
+    }
+}
+
+// x: copy_load8 of s0 = g, issued by the caller (as early as it likes)
+__device__ __forceinline__ f4 copy_sum4(const float *__restrict__ gpart, int ns, int64_t gs, int64_t ii, int g,
+                                        f4 (&x)[8]) {
     f4 acc = f4{0.0f, 0.0f, 0.0f, 0.0f};
     for (int s0 = g; s0 < ns; s0 += 32) {
-        // unconditional loads (clamped copy index), selected afterwards: a select around each
-        // load would make the compiler branch and drain per load
-        f4 x[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int sc = s0 + 4 * u;
-            x[u] = *reinterpret_cast<const f4 *>(gpart + (int64_t)(sc < ns ? sc : 0) * gs + ii);
-        }
+        if (s0 != g) copy_load8(gpart, ns, gs, ii, s0, x);
 #pragma unroll
         for (int u = 0; u < 8; ++u)
             if (s0 + 4 * u < ns) acc += x[u];
@@ -871,6 +892,12 @@ __device__ __forceinline__ f4 copy_sum4(const float *__restrict__ gpart, int ns,
     return acc;
 }
 
+__device__ __forceinline__ f4 copy_sum4(const float *__restrict__ gpart, int ns, int64_t gs, int64_t ii, int g) {
+    f4 x[8];
+    copy_load8(gpart, ns, gs, ii, g, x);
+    return copy_sum4(gpart, ns, gs, ii, g, x);
+}
+
 struct Adam4 {         // one network's Adam over its split-K copies (copy stride gs % 4 == 0)
     float *p;
     const float *gpart;
@@ -881,25 +908,27 @@ struct Adam4 {         // one network's Adam over its split-K copies (copy strid
     int ns, step_add;
 };
 
-// the copy-parallel Adam of one network by workgroups blk = 0 .. nblk-1
-__device__ __forceinline__ void adam4_body(const Adam4 &P, int64_t blk, int64_t nblk) {
+// the copy-parallel Adam of one network by workgroups blk = 0 .. nblk-1 (bc: two floats of LDS).
+// Every thread of the workgroup comes through here, a wave with no element (base >= n) included:
+// adam_bias_bcast holds the workgroup barrier, and the loop with its exits starts only after it.
+__device__ __forceinline__ void adam4_body(const Adam4 &P, int64_t blk, int64_t nblk, float *bc) {
     const int lane = threadIdx.x & 63, g = lane >> 4, e4 = lane & 15;
     const int64_t wave = blk * 4 + (threadIdx.x >> 6), nwaves = nblk * 4;
     const int t = *P.step + P.step_add;
-    const double bc1 = 1.0 - pow((double)P.b1, (double)t);
-    const double bc2 = 1.0 - pow((double)P.b2, (double)t);
-    const float step_size = (float)((double)P.lr / bc1);
-    const float bc2s = (float)sqrt(bc2);
+    int64_t base = wave * 64;
+    int64_t i = base + 4 * e4, k = i + g;
+    // the first trip's loads ahead of the bias corrections: the element's optimiser state (clamped
+    // index, unconditional) in flight with the copy loads instead of after their sum
+    int64_t kc = k < P.n ? k : P.n - 1, ic = i < P.n ? i : 0;
+    float m0 = P.m[kc], v0 = P.v[kc], p0 = P.p[kc];
+    f4 x[8];
+    copy_load8(P.gpart, P.ns, P.gs, ic, g, x);
+    float step_size, bc2s;
+    adam_bias_bcast(bc, P.lr, P.b1, P.b2, t, step_size, bc2s);
     const float w1 = (float)(1.0 - (double)P.b1), w2 = (float)(1.0 - (double)P.b2);
     const float b2 = P.b2, eps = P.eps;
-    for (int64_t base = wave * 64; base < P.n; base += nwaves * 64) {
-        const int64_t i = base + 4 * e4;
-        const int64_t k = i + g;
-        // the element's optimiser state loads first (clamped index, unconditional): in flight with the
-        // copy loads instead of after their sum
-        const int64_t kc = k < P.n ? k : P.n - 1;
-        const float m0 = P.m[kc], v0 = P.v[kc], p0 = P.p[kc];
-        const f4 acc = copy_sum4(P.gpart, P.ns, P.gs, i < P.n ? i : 0, g);
+    while (base < P.n) {
+        const f4 acc = copy_sum4(P.gpart, P.ns, P.gs, ic, g, x);
         if (k < P.n) {
             const float gi = g == 0 ? acc.x : (g == 1 ? acc.y : (g == 2 ? acc.z : acc.w));
             if (P.gout) P.gout[k] = gi;
@@ -912,16 +941,27 @@ __device__ __forceinline__ void adam4_body(const Adam4 &P, int64_t blk, int64_t 
             P.m[k] = mi;
             P.v[k] = vi;
         }
+        base += nwaves * 64;
+        if (base >= P.n) break;
+        i = base + 4 * e4, k = i + g;
+        kc = k < P.n ? k : P.n - 1, ic = i < P.n ? i : 0;
+        m0 = P.m[kc], v0 = P.v[kc], p0 = P.p[kc];
+        copy_load8(P.gpart, P.ns, P.gs, ic, g, x);
     }
 }
 
-__global__ void __launch_bounds__(256) adam_sum4_kernel(Adam4 P) { adam4_body(P, blockIdx.x, gridDim.x); }
+__global__ void __launch_bounds__(256) adam_sum4_kernel(Adam4 P) {
+    __shared__ float bc[2];
+    adam4_body(P, blockIdx.x, gridDim.x, bc);
+}
 
 // two networks in one launch (the critic step of iteration i+1 and the actor step of iteration i
-// end together): workgroups [0, g1) take the first, the rest the second
+// end together): workgroups [0, g1) take the first, the rest the second (a workgroup-uniform branch,
+// so each side's barrier is reached by whole workgroups)
 __global__ void __launch_bounds__(256) adam_sum4_pair_kernel(Adam4 P0, Adam4 P1, int g1) {
-    if ((int)blockIdx.x < g1) adam4_body(P0, blockIdx.x, g1);
-    else adam4_body(P1, blockIdx.x - g1, gridDim.x - g1);
+    __shared__ float bc[2];
+    if ((int)blockIdx.x < g1) adam4_body(P0, blockIdx.x, g1, bc);
+    else adam4_body(P1, blockIdx.x - g1, gridDim.x - g1, bc);
 }
 
 __global__ void __launch_bounds__(256) sum_partials4_kernel(float *out, const float *__restrict__ gpart, int ns,
@@ -2692,6 +2732,7 @@ int aac_adam_flat_sum_strided(float *p, const float *gpart, int32_t ns, int64_t 
                               void *stream) {
     if (ns < 1) return ffail("adam_flat_sum: nsplit >= 1");
     if (gstride < n) return ffail("adam_flat_sum: copy stride < n");
+    if (n < 1) return 0;            // the kernels load element min(i, n - 1) unconditionally
     if (use_sum4(gpart, ns, gstride)) {
         const Adam4 P{p, gpart, gout, m, v, step, gstride, n, lr, b1, b2, eps, ns, step_add};
         hipLaunchKernelGGL(adam_sum4_kernel, dim3(sum4_grid(n)), dim3(256), 0, (hipStream_t)stream, P);

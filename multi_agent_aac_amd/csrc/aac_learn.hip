@@ -19,6 +19,7 @@
 #include "../../include/aac_learn.h"
 #include "aac_wave.h"
 #include "aac_noise.h"
+#include "aac_adam_bc.h"
 
 using aacn::row_noise;
 using aacn::take_epoch;
@@ -313,22 +314,30 @@ __global__ void __launch_bounds__(LEARN_BLOCK) gather_kernel(const float *ring, 
 // ranks' gradients without a separate division launch; exact for power-of-two worlds)
 __global__ void adam_kernel(float *p, const float *g, float *m, float *v, int64_t n, float lr, float b1, float b2,
                             float eps, const int32_t *step, int step_add, float gscale) {
+    __shared__ float bc[2];
     const int t = *step + step_add;
-    const double bc1 = 1.0 - pow((double)b1, (double)t);
-    const double bc2 = 1.0 - pow((double)b2, (double)t);
-    const float step_size = (float)((double)lr / bc1);
-    const float bc2s = (float)sqrt(bc2);
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    // the first trip's loads go out ahead of the bias corrections (clamped index, unconditional: a
+    // thread past n still reaches the barrier in adam_bias_bcast)
+    const int64_t ic = i < n ? i : n - 1;
+    float g0 = g[ic], m0 = m[ic], v0 = v[ic], p0 = p[ic];
+    float step_size, bc2s;
+    adam_bias_bcast(bc, lr, b1, b2, t, step_size, bc2s);
     const float w1 = (float)(1.0 - (double)b1), w2 = (float)(1.0 - (double)b2);
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float gi = g[i] * gscale;
-        float mi = m[i];
+    while (i < n) {
+        const float gi = g0 * gscale;
+        float mi = m0;
         mi = mi + w1 * (gi - mi);               // exp_avg.lerp_(grad, 1 - beta1)
-        float vi = v[i] * b2;                   // exp_avg_sq.mul_(beta2)
+        float vi = v0 * b2;                     // exp_avg_sq.mul_(beta2)
         vi = vi + w2 * (gi * gi);               //   .addcmul_(grad, grad, 1 - beta2)
         const float den = sqrtf(vi) / bc2s + eps;
-        p[i] = p[i] + (-step_size) * (mi / den);   // param.addcdiv_(exp_avg, denom, -step_size)
+        p[i] = p0 + (-step_size) * (mi / den);     // param.addcdiv_(exp_avg, denom, -step_size)
         m[i] = mi;
         v[i] = vi;
+        i += stride;
+        if (i >= n) break;
+        g0 = g[i], m0 = m[i], v0 = v[i], p0 = p[i];
     }
 }
 
@@ -794,6 +803,7 @@ int aac_adam_flat_at(float *p, const float *g, float *m, float *v, int64_t n, fl
 
 int aac_adam_flat_at_scaled(float *p, const float *g, float *m, float *v, int64_t n, float lr, float b1, float b2,
                             float eps, const int32_t *step, int32_t step_add, float gscale, void *stream) {
+    if (n < 1) return 0;            // the kernel loads element min(i, n - 1) unconditionally
     hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n)), dim3(LEARN_BLOCK), 0, (hipStream_t)stream, p, g, m, v, n, lr,
                        b1, b2, eps, step, step_add, gscale);
     LHIP(hipGetLastError());

@@ -20,6 +20,7 @@
 #include <string>
 
 #include "../../include/aac_uam_learn.h"
+#include "aac_adam_bc.h"
 
 namespace {
 
@@ -262,11 +263,17 @@ __global__ void __launch_bounds__(256) uam_td_mse_head_kernel(const double *__re
 __global__ void adam64_kernel(double *p, const double *__restrict__ gpart, int ns, double *m, double *v, int64_t n,
                               double lr, double b1, double b2, double eps, const int32_t *step, int step_add,
                               double gscale) {
+    __shared__ double bc[2];
     const int t = *step + step_add;
-    const double bc1 = 1.0 - pow(b1, (double)t), bc2 = 1.0 - pow(b2, (double)t);
-    const double step_size = lr / bc1, bc2s = sqrt(bc2);
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        double gi = gpart[i];
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    // the first trip's loads go out ahead of the bias corrections (clamped index, unconditional: a
+    // thread past n still reaches the barrier in adam_bias_bcast)
+    const int64_t ic = i < n ? i : n - 1;
+    double gi = gpart[ic], m0 = m[ic], v0 = v[ic], p0 = p[ic];
+    double step_size, bc2s;
+    adam_bias_bcast(bc, lr, b1, b2, t, step_size, bc2s);
+    while (i < n) {
         int s = 1;
         for (; s + 8 <= ns; s += 8) {
             double x[8];
@@ -277,12 +284,15 @@ __global__ void adam64_kernel(double *p, const double *__restrict__ gpart, int n
         }
         for (; s < ns; ++s) gi += gpart[(int64_t)s * n + i];
         gi *= gscale;           // 1 / world after a SUM all-reduce (1 otherwise); the mean exactly for power-of-two worlds
-        const double mi = b1 * m[i] + (1.0 - b1) * gi;
-        const double vi = b2 * v[i] + (1.0 - b2) * gi * gi;
+        const double mi = b1 * m0 + (1.0 - b1) * gi;
+        const double vi = b2 * v0 + (1.0 - b2) * gi * gi;
         const double den = sqrt(vi) / bc2s + eps;
-        p[i] = p[i] - step_size * mi / den;
+        p[i] = p0 - step_size * mi / den;
         m[i] = mi;
         v[i] = vi;
+        i += stride;
+        if (i >= n) break;
+        gi = gpart[i], m0 = m[i], v0 = v[i], p0 = p[i];
     }
 }
 
