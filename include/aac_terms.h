@@ -3,8 +3,8 @@
  *
  * The reference hands its loop the pieces of every reward (ATT/env:2590 step_reward_record,
  * :2596-2620 eps_status_holder; WGRU/env:1666-2039).  With a terms buffer attached
- * (aac_env_set_terms_buffer, aac_env.h) the step kernels of variants 0 (ATT) and 1 (WGRU) store one row
- * of AAC_TERMS_W doubles per (env, agent): double terms[E][N][AAC_TERMS_W].
+ * (aac_env_set_terms_buffer, aac_env.h) the step kernels of variants 0 (ATT) and 1 (WGRU), and the UAM step
+ * kernel (below), store one row of AAC_TERMS_W doubles per (env, agent): double terms[E][N][AAC_TERMS_W].
  *
  * Contribution slots 0..7: what the taken branch added to the agent's own reward, sign included, 0
  * where the branch leaves the term out.  The left-to-right double sum ((((((s0+s1)+s2)+s3)+s4)+s5)+s6)
@@ -23,6 +23,14 @@
  *   10 goal_dist   distance after the step to the point the progress term measures against
  *                  (goal[-1] in ATT, the next waypoint in WGRU)
  *   11 radar_min   the radar minimum the near-building penalty used (0 in ATT)
+ * UAM (aac_uam_set_terms_buffer, aac_uam.h; UAM/env:3892-4629), the same slots:
+ *   0 event     -crash on a bound crash, a cloud / runway conflict or a drone collision, +50 on the goal
+ *               branch; crash = 50 * 2^(collision-bearing doublings among aircraft 0..i of this call)
+ *   3 progress  dist_to_goal, 5 building  -near_building, 6 drone  -near_drone = -(ndc * (m * shortest + c))
+ *               or -(ndc * 0) with the doubled ndc in effect for this aircraft: normal branch only, else 0
+ *   1, 2, 4, 7  0
+ *   8 cross_track  distance to the nearest point of the reference line start -> goal
+ *   9 speed_norm, 10 goal_dist (to goal[-1]), 11 radar_min (over the 18 rays): every branch
  * A finished env keeps its terminal step's rows: resets (in-launch or not) never write terms.  The
  * exact-threshold fix-up that rewrites a WGRU reward rewrites that row's slots 5 and 11 with it.
  *

@@ -79,6 +79,15 @@ void aac_uam_set_reset_compact(int32_t on);
  * keeps it alive while the handle exists.  The copy is enqueued on `stream`. */
 int aac_uam_use_episode_buffer(aac_uam *env, int32_t *episode_dev, void *stream);
 
+/* Reward terms (aac_terms.h): attaches the caller's device buffer double[E][N][AAC_TERMS_W] (16-byte
+ * aligned, kept alive while attached); NULL detaches it.  While attached, aac_uam_step launches the
+ * step kernel's terms form, which stores every aircraft's row: the taken branch's terms with the crash
+ * and near-drone coefficients in effect for that aircraft (their doubling persists over the later
+ * aircraft of the call), and the gauges.  While detached the launch is the plain one.  Resets never
+ * write terms.  Host-side only (no launch): it takes effect with the next step call; a captured graph
+ * keeps the form it was captured with. */
+int aac_uam_set_terms_buffer(aac_uam *env, double *terms_dev);
+
 /* Flight recorder (aac_record.h): aac_record with E and the state sources of ``step`` (pos, vel, goal,
  * heading, clouds and the episode counter, wherever aac_uam_use_episode_buffer has put it; no map_idx)
  * filled from the handle's live device pointers at call time.  The double actions are stored as float.

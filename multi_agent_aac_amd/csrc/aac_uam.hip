@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/aac_uam.h"
+#include "../../include/aac_terms.h"
 #include "aac_geom.h"
 #include "aac_wave.h"
 
@@ -698,7 +699,13 @@ __device__ __attribute__((always_inline)) void reset_envs(const UArgs &A, const 
 // (the replay push inside this launch was built, bit-exact, and measured slower: the launch grew 188 ->
 // 234 us against the 23-us push launch it replaced; so was the bank reset of the finished envs in it,
 // config 5 226 vs 238 M agent-env-steps/s; round 5, removed in round 6)
-__global__ void __launch_bounds__(BLOCK, AAC_UAM_MIN_WAVES) uam_step_kernel(UArgs A, const double2 *__restrict__ act) {
+// TERMS: every aircraft's reward-terms row (include/aac_terms.h) goes to terms[E][N][AAC_TERMS_W].  Phase
+// 5's thread owns the aircraft and stores slots 2-5 and 8-11 from its registers; phase 6 stores slots 0,
+// 1, 6 and 7, which need the prefix coefficients.  No LDS beyond the plain form's; terms is not read
+// when TERMS is false.
+template <bool TERMS>
+__global__ void __launch_bounds__(BLOCK, AAC_UAM_MIN_WAVES) uam_step_kernel(UArgs A, const double2 *__restrict__ act,
+                                                                            double *__restrict__ terms) {
     __shared__ Lds S;
 
     const int N = A.N, K = A.K;
@@ -831,7 +838,8 @@ __global__ void __launch_bounds__(BLOCK, AAC_UAM_MIN_WAVES) uam_step_kernel(UArg
         const double rdx = g.x - s.x, rdy = g.y - s.y;
         double fr = ((px - s.x) * rdx + (py - s.y) * rdy) / (rdx * rdx + rdy * rdy);
         fr = fr < 0.0 ? 0.0 : (fr > 1.0 ? 1.0 : fr);
-        const double left = gdist(px, py, s.x + fr * rdx, s.y + fr * rdy) + (L - fr * L);
+        const double cross = gdist(px, py, s.x + fr * rdx, s.y + fr * rdy);
+        const double left = cross + (L - fr * L);
         const double dtg = 5.0 * (1 - (left / L));
         // near-drone band (UAM/env:4305-4327); near-building penalty (UAM/env:4466-4481)
         uint8_t fl = 0;
@@ -845,6 +853,12 @@ __global__ void __launch_bounds__(BLOCK, AAC_UAM_MIN_WAVES) uam_step_kernel(UArg
         double mn = S.rad[t][0];
         for (int r = 1; r < NRAY; ++r) mn = S.rad[t][r] < mn ? S.rad[t][r] : mn;
         const double nbp = (mn >= pb && mn <= 5.0) ? 2.0 * (((0 - 1) / (5.0 - pb)) * mn + 2) : 0.0;
+        if constexpr (TERMS) {      // the gauges: every branch writes them
+            const double2 v = S.vel[t];
+            double2 *q = reinterpret_cast<double2 *>(terms + ai * AAC_TERMS_W);
+            q[4] = make_double2(cross, npnorm(v.x, v.y));
+            q[5] = make_double2(npnorm(px - g.x, py - g.y), mn);
+        }
         const int bnd = capsule_crash(pb, A.bound, pp.x, pp.y, px, py);
         uint8_t kind;
         if (bnd) kind = 0;
@@ -860,6 +874,11 @@ __global__ void __launch_bounds__(BLOCK, AAC_UAM_MIN_WAVES) uam_step_kernel(UArg
         S.flag[t] = fl;
         S.nd_val[t] = ndv;
         S.base[t] = (0 + dtg) - nbp;
+        if constexpr (TERMS) {      // path 0, progress, speed 0, building: the normal branch's, else 0
+            double2 *q = reinterpret_cast<double2 *>(terms + ai * AAC_TERMS_W);
+            q[1] = make_double2(0.0, kind == 4 ? dtg : 0.0);
+            q[2] = make_double2(0.0, kind == 4 ? -nbp : 0.0);
+        }
         A.mask[ai] = (uint8_t)(bnd | (cloud << 1) | ((ncoll > 0) << 2) | (goal << 3) | ((kind == 3) << 4) |
                                ((kind == 2 && prev_two) << 5));
         if (kind == 3) S.reach[t] = 1;
@@ -909,6 +928,11 @@ __global__ void __launch_bounds__(BLOCK, AAC_UAM_MIN_WAVES) uam_step_kernel(UArg
                 const size_t aj = (size_t)eq * N + j;
                 A.reward[aj] = rew;
                 A.done[aj] = (uint8_t)dn;
+                if constexpr (TERMS) {      // event and drone (waypoint and reserved 0)
+                    double2 *q = reinterpret_cast<double2 *>(terms + aj * AAC_TERMS_W);
+                    q[0] = make_double2(kind < 3 ? -crash : (kind == 3 ? 50.0 : 0.0), 0.0);
+                    q[3] = make_double2(kind == 4 ? -nd : 0.0, 0.0);
+                }
             }
             const unsigned long long m_done = __ballot(on && dn), m_nreach = __ballot(on && !rch);
             const unsigned long long m_k0 = __ballot(on && kind == 0), m_k1 = __ballot(on && kind == 1);
@@ -961,6 +985,11 @@ __global__ void __launch_bounds__(BLOCK, AAC_UAM_MIN_WAVES) uam_step_kernel(UArg
             const size_t aj = (size_t)eq * N + j;
             A.reward[aj] = rew;
             A.done[aj] = (uint8_t)dn;
+            if constexpr (TERMS) {
+                double2 *q = reinterpret_cast<double2 *>(terms + aj * AAC_TERMS_W);
+                q[0] = make_double2(kind < 3 ? -crash : (kind == 3 ? 50.0 : 0.0), 0.0);
+                q[3] = make_double2(kind == 4 ? -nd : 0.0, 0.0);
+            }
             any_done |= dn;
             all_reach &= S.reach[la];
         }
@@ -1140,6 +1169,7 @@ struct aac_uam {
     uint64_t bank_seed;
     int32_t *rlist;           // [1 + E]: compacted resetting envs of the last auto-reset
     int32_t *episode_own;     // the handle's own counter buffer (episode may be a caller's buffer)
+    double *terms;            // caller's reward-terms buffer (aac_uam_set_terms_buffer), null: detached
 };
 
 static size_t dist_bytes(const aac_uam *h) { return sizeof(double) * (size_t)h->epb * h->cfg.N * h->cfg.N; }
@@ -1278,8 +1308,12 @@ int aac_uam_step(aac_uam *h, const double *actions, const aac_uam_out *o, void *
     if (rc) return rc;
     if (!o->reward || !o->done || !o->mask || !o->env_done || !o->bbc) return ufail(AAC_E_INVALID, "step outputs");
     UArgs A = make_uargs(h, o);
-    hipLaunchKernelGGL(uam_step_kernel, dim3(h->blocks), dim3(BLOCK), dist_bytes(h), (hipStream_t)stream, A,
-                       reinterpret_cast<const double2 *>(actions));
+    if (h->terms)
+        hipLaunchKernelGGL(uam_step_kernel<true>, dim3(h->blocks), dim3(BLOCK), dist_bytes(h), (hipStream_t)stream, A,
+                           reinterpret_cast<const double2 *>(actions), h->terms);
+    else
+        hipLaunchKernelGGL(uam_step_kernel<false>, dim3(h->blocks), dim3(BLOCK), dist_bytes(h), (hipStream_t)stream, A,
+                           reinterpret_cast<const double2 *>(actions), (double *)nullptr);
     UCHK(hipGetLastError());
     return AAC_OK;
 }
@@ -1337,6 +1371,14 @@ int aac_uam_use_episode_buffer(aac_uam *h, int32_t *episode_dev, void *stream) {
         UCHK(hipMemcpyAsync(episode_dev, h->episode, sizeof(int32_t) * (size_t)h->cfg.E, hipMemcpyDeviceToDevice,
                             (hipStream_t)stream));
     h->episode = episode_dev;
+    return AAC_OK;
+}
+
+int aac_uam_set_terms_buffer(aac_uam *h, double *terms_dev) {
+    if (!h) return ufail(AAC_E_INVALID, "null handle");
+    if (reinterpret_cast<uintptr_t>(terms_dev) & 15)
+        return ufail(AAC_E_INVALID, "set_terms_buffer: the buffer must be 16-byte aligned (rows are stored as double2)");
+    h->terms = terms_dev;
     return AAC_OK;
 }
 

@@ -25,7 +25,7 @@ class Evaluator:
     """``evaluate(k)`` plays k episodes in each of E eval envs and returns their statistics
     (``EpisodeStats.read()``: exactly E * k episodes).
 
-    ``terms=True`` (ATT and GRU trainers): the eval env gets a reward-terms buffer and a reward ledger
+    ``terms=True`` (ATT, GRU and UAM trainers): the eval env gets a reward-terms buffer and a reward ledger
     (``terms.RewardLedger``) fed beside the statistics under the same quota, so it holds the same
     episode set; ``evaluate`` then returns ``(stats, ledger.read())`` and ``record``
     ``(stats, Trajectories, ledger.read())``, the trajectories with a ``terms`` array."""
@@ -60,7 +60,7 @@ class Evaluator:
         self.ledger = None
         if terms:
             from .terms import RewardLedger
-            self.ledger = RewardLedger.for_env(self.env)      # NotImplementedError for the UAM env
+            self.ledger = RewardLedger.for_uam(self.env) if self.uam else RewardLedger.for_env(self.env)
         if self.gru:
             from . import gru
             # hidden states as the trainer's ping-pong pair, and act plans of this object's own: the
@@ -87,6 +87,8 @@ class Evaluator:
             act = self.model.act(c.own, c.radar, self.episode, noisy=False)
             self.env.step(act, out=n)
             self.stats.accumulate(n, quota=self.quota)
+            if self.ledger is not None:
+                self.ledger.accumulate(n, quota=self.quota)
             self.env.auto_reset(n.env_done, out=n)
             return
         elif self.gru:

@@ -153,9 +153,9 @@ class FlightRecorder:
         self.env_ids = torch.as_tensor(ids, device=d)
         tt = {"<i4": torch.int32, "<f8": torch.float64, "<f4": torch.float32, "u1": torch.uint8}
         self.track = {k: torch.zeros(self.T, dtype=tt[dt], device=d) for k, dt in TRACK_FIELDS}
-        # an env with a reward-terms buffer (BatchedEnv.use_terms_buffer) attached when the recorder is
+        # an env with a reward-terms buffer (use_terms_buffer) attached when the recorder is
         # built: its rows are recorded too
-        self.terms_src = None if self.uam else getattr(env, "terms", None)
+        self.terms_src = getattr(env, "terms", None)
         self.rows = {k: torch.zeros(self.T, self.S, *shp, dtype=tt[dt], device=d)
                      for k, (dt, shp) in row_fields(N, heading=self.uam, clouds=self.uam,
                                                     terms=self.terms_src is not None).items()}

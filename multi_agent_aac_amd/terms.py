@@ -1,16 +1,18 @@
 """Reward ledger (include/aac_terms.h): which terms an episode's return is made of, kept on the device.
 
-With a terms buffer attached (``BatchedEnv.use_terms_buffer``) the env step kernels store one row of
-``WIDTH`` doubles per (env, agent): the eight contribution slots ``CONTRIB`` -- what the taken reward
-branch added, sign included; their left-to-right sum is the agent's own reward -- and four gauges.
-``RewardLedger.accumulate(bufs)`` is one small launch after each env step on torch's current stream (it
-may be captured in a HIP graph with the step) and keeps, per finished episode, the sum of every
-contribution slot over the episode's steps and agents; ``read()`` folds the per-workgroup slots and
-downloads count, mean, std, min, max and each slot's share of the mean return.
+With a terms buffer attached (``BatchedEnv.use_terms_buffer``, ``BatchedUAM.use_terms_buffer``) the env
+step kernels store one row of ``WIDTH`` doubles per (env, agent): the eight contribution slots ``CONTRIB``
+-- what the taken reward branch added, sign included; their left-to-right sum is the agent's own reward --
+and four gauges.  ``RewardLedger.accumulate(bufs)`` is one small launch after each env step on torch's
+current stream (it may be captured in a HIP graph with the step) and keeps, per finished episode, the sum
+of every contribution slot over the episode's steps and agents; ``read()`` folds the per-workgroup slots
+and downloads count, mean, std, min, max and each slot's share of the mean return.
 
-Scope: the ATT and WGRU variants of ``BatchedEnv``.  The UAM and MPE envs emit no terms; with several
-ranks each rank keeps its own ledger; a checkpoint does not carry the ledger (a resumed run starts an
-empty one).
+Scope: the ATT and WGRU variants of ``BatchedEnv`` (``RewardLedger.for_env``) and the UAM env
+(``BatchedUAM``, ``RewardLedger.for_uam``), whose rows carry the order-dependent crash and near-drone
+coefficients in effect for each aircraft.  The MPE env emits
+no terms; with several ranks each rank keeps its own ledger; a checkpoint does not carry the ledger (a
+resumed run starts an empty one).
 """
 import ctypes
 import math
@@ -68,11 +70,22 @@ class RewardLedger:
 
     @classmethod
     def for_env(cls, env):
-        """For a ``BatchedEnv`` (att or wgru).  The env's terms buffer is attached if it has none."""
+        """For a ``BatchedEnv`` (att or wgru).  The env's terms buffer is attached if it has none.  Any
+        other env is refused, as before the UAM env had terms: a ``BatchedUAM`` goes through ``for_uam``."""
         from .env import BatchedEnv
         if not isinstance(env, BatchedEnv):
-            raise NotImplementedError(f"RewardLedger: {type(env).__name__} emits no reward terms; the ledger covers "
-                                      "the ATT and WGRU variants of BatchedEnv (not the UAM or MPE envs)")
+            raise NotImplementedError(f"RewardLedger.for_env: {type(env).__name__} is no BatchedEnv; it covers the ATT "
+                                      "and WGRU variants (the UAM env: RewardLedger.for_uam; the MPE env emits no terms)")
+        if env.terms is None:
+            env.use_terms_buffer()
+        return cls(env)
+
+    @classmethod
+    def for_uam(cls, env):
+        """For a ``BatchedUAM``.  The env's terms buffer is attached if it has none."""
+        from .uam import BatchedUAM
+        if not isinstance(env, BatchedUAM):
+            raise NotImplementedError(f"RewardLedger.for_uam: {type(env).__name__} is no BatchedUAM")
         if env.terms is None:
             env.use_terms_buffer()
         return cls(env)
@@ -86,8 +99,8 @@ class RewardLedger:
         sd[:, F_MAX:] = -math.inf
 
     def accumulate(self, bufs, quota=None):
-        """Add the step whose outputs are in ``bufs`` (``StepBuffers``; its ``env_done`` is read) and
-        whose terms are in the env's attached buffer, after the step launch on the same stream.
+        """Add the step whose outputs are in ``bufs`` (``StepBuffers`` / ``UamBuffers``; its ``env_done`` is
+        read) and whose terms are in the env's attached buffer, after the step launch on the same stream.
         ``quota``: int32 [E] tensor (or an int, kept in ``self.quota``), the rule of
         ``EpisodeStats.accumulate``: an env with that many finished episodes contributes nothing more."""
         if isinstance(quota, int):

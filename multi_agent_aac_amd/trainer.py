@@ -436,9 +436,14 @@ class UamTrainer(CheckpointMixin):
     ``stats=True``: episode tallies in ``self.stats``, checkpointed and returned by ``finish()`` as
     ``Trainer``'s (a file saved without them raises a KeyError naming the tensor on load).
     ``monitor=True`` (or a ring length): the learner's records in ``self.monitor`` as ``Trainer``'s (one
-    column, float64)."""
+    column, float64).
+    ``terms=True``: a reward-terms buffer on the env and the per-episode totals of the terms in
+    ``self.ledger`` as ``Trainer``'s: one small launch after the stats launch position of every env step,
+    eager or inside the whole-step graphs, on the main stream before the auto-reset forks to its side
+    stream (the reset touches neither the terms nor ``env_done``).  Off (the default) the launches are
+    unchanged and ``self.ledger`` is None."""
 
-    def __init__(self, E, N, B, memory, seed, pg=None, stats=False, monitor=False):
+    def __init__(self, E, N, B, memory, seed, pg=None, stats=False, monitor=False, terms=False):
         from . import uam, uam_learner
         self.E, self.N, self.B = E, N, B
         self.gru = False
@@ -462,6 +467,10 @@ class UamTrainer(CheckpointMixin):
         self._pos_dirty = True
         self._init_stats(stats)
         self._init_monitor(monitor, 1, torch.float64)
+        self.ledger = None
+        if terms:       # the env's step launches take their terms form from here on (no graph exists yet)
+            from .terms import RewardLedger
+            self.ledger = RewardLedger.for_uam(self.env)
 
     def graph_ok(self):
         """Whole-step graphs: one rank, the fused learner, the replay past one batch, no hooks."""
@@ -481,6 +490,8 @@ class UamTrainer(CheckpointMixin):
         self.env.step(act, out=n)
         if self.stats is not None:
             self.stats.accumulate(n)
+        if self.ledger is not None:
+            self.ledger.accumulate(n)
         self.replay.push_batch(c.own, c.radar, act, n.reward, n.done, n.own, n.radar,
                                pos_io=(self.pos_dev[p], self.pos_dev[1 - p]))
         fu = self.model.fused(self.B, self.replay)
@@ -564,6 +575,8 @@ class UamTrainer(CheckpointMixin):
             self.env.step(act, out=n)
             if self.stats is not None:
                 self.stats.accumulate(n)
+            if self.ledger is not None:
+                self.ledger.accumulate(n)
         if time_env:
             ev1.record()
             self.env_events.append((ev0, ev1))

@@ -27,7 +27,7 @@ BOUND = (0.0, 40.0, 0.0, 40.0)               # UAM/params:32-36
 EXPORTS = ("aac_uam_create", "aac_uam_destroy", "aac_uam_last_error", "aac_uam_reset", "aac_uam_step",
            "aac_uam_set_bank", "aac_uam_auto_reset", "aac_uam_bank_build", "aac_uam_get_state",
            "aac_uam_set_state", "aac_uam_actor", "aac_uam_actor_last_error", "aac_uam_set_reset_compact",
-           "aac_uam_use_episode_buffer")
+           "aac_uam_use_episode_buffer", "aac_uam_set_terms_buffer")
 
 
 class UamCfg(ctypes.Structure):
@@ -59,6 +59,7 @@ def lib():
         L.aac_uam_set_reset_compact.argtypes = [i32]
         L.aac_uam_set_reset_compact.restype = None
         L.aac_uam_use_episode_buffer.argtypes = [vp, vp, vp]
+        L.aac_uam_set_terms_buffer.argtypes = [vp, vp]
         L.aac_uam_bank_build.argtypes = [i32, i32, ctypes.c_uint64, vp, vp, vp]
         L.aac_uam_get_state.argtypes = [vp] + [vp] * 13 + [vp]
         L.aac_uam_set_state.argtypes = [vp] + [vp] * 13 + [vp]
@@ -156,6 +157,7 @@ class BatchedUAM:
         self._h = h
         self.bufs = self.alloc_buffers()
         self.bank = None
+        self.terms = None       # the attached reward-terms buffer (use_terms_buffer)
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -226,6 +228,23 @@ class BatchedUAM:
         _chk(lib().aac_uam_use_episode_buffer(self._h, _ptr(episode), _stream()), "aac_uam_use_episode_buffer")
         self._episode_buf = episode
         return episode
+
+    def use_terms_buffer(self, t=None, detach=False):
+        """Attach a reward-terms buffer (float64 [E][N][12], include/aac_terms.h): ``t``, or a new one;
+        ``env.terms`` holds it.  From the next step on the step kernel stores every aircraft's reward
+        terms in it (a captured graph keeps the form it was captured with); resets never write it.
+        ``detach=True`` detaches it: the step launches are the plain ones again."""
+        if detach:
+            t = None
+        else:
+            if t is None:
+                t = torch.zeros(self.E, self.N, 12, dtype=torch.float64, device=self.device)
+            if t.dtype != torch.float64 or tuple(t.shape) != (self.E, self.N, 12) or not t.is_contiguous() \
+                    or t.device != self.device:
+                raise ValueError(f"terms buffer: float64 ({self.E}, {self.N}, 12), contiguous, on {self.device}")
+        _chk(lib().aac_uam_set_terms_buffer(self._h, _ptr(t)), "aac_uam_set_terms_buffer")
+        self.terms = t
+        return t
 
     def auto_reset(self, env_done=None, out: Optional[UamBuffers] = None):
         """Reset every env with env_done != 0 (None = all) to a fresh bank episode."""
@@ -298,10 +317,16 @@ class CloudView:
 class env_simulator:
     """Reference-compatible facade (E = 1) over ``BatchedUAM``.  The UAM map has no buildings in
     the observation or reward path (radar and conflicts use the runway, the bound, the clouds and
-    the other aircraft), so ``world_map`` / ``building_polygons`` are accepted and kept only."""
+    the other aircraft), so ``world_map`` / ``building_polygons`` are accepted and kept only.
+
+    ``reward_terms=True`` attaches a reward-terms buffer (include/aac_terms.h) and
+    ``ss_reward_Mar_changeskin`` fills ``eps_status_holder[i]`` with the per-step pieces the reference hands
+    its loop (UAM/env:4651-4665) that the kernel supplies, penalties unsigned as there:
+    ``goal_leading_reward``, ``near_building_penalty``, ``near_drone_penalty``, ``current_drone_speed``,
+    ``Euclidean_dist_to_goal``, and ``deviation_to_ref_line`` (the cross-track gauge, an extra key)."""
 
     def __init__(self, world_map=None, building_polygons=None, grid_length=1, bound=None, allGridPoly=None,
-                 agentConfig=None, seed=None):
+                 agentConfig=None, seed=None, reward_terms=False):
         self.world_map_2D = world_map
         self.buildingPolygons = building_polygons
         self.world_map_2D_polyList = allGridPoly
@@ -315,6 +340,7 @@ class env_simulator:
         self._seed = 0 if seed is None else int(seed)
         self._draws = 0
         self._env = None
+        self.reward_terms = bool(reward_terms)
 
     def create_world(self, total_agentNum, n_actions, gamma, tau, target_update, largest_Nsigma, smallest_Nsigma,
                      ini_Nsigma, max_xy, max_spd, acc_range):
@@ -327,6 +353,8 @@ class env_simulator:
         self.dummy_agent = self.all_agents[0]
         self._env = BatchedUAM(1, total_agentNum, vmax=float(max_spd), acc_max=float(abs(acc_range[1])),
                                bound=self.bound, p3=True)
+        if self.reward_terms:
+            self._env.use_terms_buffer()
 
     def reset_world_change_skin(self, total_agentNum, full_observable_critic_flag=False, evaluation_by_fixed_ar=False,
                                 include_other_AC=True, use_nearestN_neigh_wRadar=False, N_neigh=2, args=None,
@@ -406,6 +434,8 @@ class env_simulator:
         self._env.step(a)
         b = self._env.bufs
         self._last = {k: getattr(b, k)[0].cpu().numpy() for k in ("reward", "done", "mask", "bbc")}
+        if self.reward_terms:
+            self._last["terms"] = self._env.terms[0].cpu().numpy()
         self._sync()
         state, norm = self._states()
         return state, norm, [], [], [], [], [], []
@@ -423,6 +453,13 @@ class env_simulator:
         done = [bool(last["done"][i]) for i in range(N)]
         check_goal = [bool(mask[i] & 16) for i in range(N)]
         eps_status_holder = [{} for _ in range(N)]
+        if self.reward_terms:       # slots of include/aac_terms.h; the reference lists penalties unsigned
+            for i in range(N):
+                t = last["terms"][i]
+                eps_status_holder[i] = {
+                    "goal_leading_reward": float(t[3]), "near_building_penalty": float(-t[5]),
+                    "current_drone_speed": float(t[9]), "Euclidean_dist_to_goal": float(t[10]),
+                    "near_drone_penalty": float(-t[6]), "deviation_to_ref_line": float(t[8])}
         for i, ag in self.all_agents.items():
             ag.bound_collision |= bool(mask[i] & 1)
             ag.cloud_collision |= bool(mask[i] & 2)

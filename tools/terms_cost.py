@@ -3,6 +3,8 @@ loops, in one process, alternating, on ONE trainer (the method of tools/monitor_
 
   config 3   Trainer(4096, 5, B = 1024, replay 1e5, combined radar), ``step_graph_pair``
   config 4   Trainer(4096, 8, B = 512, replay 1e5, model="gru"), ``step_graph_pair``
+  config 5   UamTrainer(8192, 16, B = 512, replay 2^20), host-launched ``step`` (its whole-step graph is
+             off by default)
 
 The trainer is built with ``terms=True``, pre-filled and warmed up.  "Off" is the same trainer with the
 terms buffer detached from the env (its step launches are the plain instantiations again), no ledger
@@ -11,7 +13,7 @@ turn (off, on, off, on, ...), a host clock around work that ends in a device syn
 config: every round's ms per step, the medians, on - off, their ratio and the spread (max - min) of the
 off rounds, which is what a difference has to exceed to mean anything.
 
-    python tools/terms_cost.py [--configs 3 4] [--rounds 6] [--steps 400] > profiles/terms_cost.txt
+    python tools/terms_cost.py [--configs 3 4 5] [--rounds 6] [--steps 400] > profiles/terms_cost.txt
 """
 import argparse
 import os
@@ -27,6 +29,8 @@ from multi_agent_aac_amd import trainer  # noqa: E402
 
 
 def build(config):
+    if config == 5:
+        return trainer.UamTrainer(8192, 16, 512, 1 << 20, seed=0, terms=True)
     if config == 4:
         return trainer.Trainer(4096, 8, 512, 100000, "combined", seed=0, model="gru", terms=True)
     return trainer.Trainer(4096, 5, 1024, 100000, "combined", seed=0, terms=True)
