@@ -24,6 +24,7 @@ EXPORTS = (
     "aac_monitor_last_error", "aac_monitor_vec", "aac_monitor_commit",
     "aac_env_set_terms_buffer", "aac_terms_last_error", "aac_terms_names", "aac_terms_accumulate", "aac_terms_reduce",
     "aac_terms_record",
+    "aac_clip_last_error", "aac_clip_partials", "aac_clip_sumsq", "aac_adam_flat_clip",
 )
 
 vp = ctypes.c_void_p
@@ -113,6 +114,13 @@ class MonitorCommitArgs(ctypes.Structure):  # aac_monitor_commit_args
                [(n, vp) for n in ("scratch", "rec", "ring", "ring_update", "agg", "state")]
 
 
+class ClipJob(ctypes.Structure):           # aac_clip_job (include/aac_clip.h)
+    _fields_ = [(n, vp) for n in ("g", "grad_out", "param", "exp_avg", "exp_avg_sq", "step", "partials", "record")] + \
+               [(n, ctypes.c_int64) for n in ("n", "gstride", "seg_stride")] + \
+               [(n, i32) for n in ("nsplit", "nseg", "order", "step_add")] + \
+               [(n, ctypes.c_double) for n in ("gscale", "max_norm", "lr", "beta1", "beta2", "eps")]
+
+
 _lib = None
 
 
@@ -165,6 +173,12 @@ def lib():
         L.aac_terms_accumulate.argtypes = [ctypes.POINTER(TermsState), ctypes.POINTER(TermsStep), vp]
         L.aac_terms_reduce.argtypes = [ctypes.POINTER(TermsState), i32, vp, i32, vp]
         L.aac_terms_record.argtypes = [ctypes.POINTER(TermsRecord), vp]
+    if hasattr(L, "aac_clip_sumsq") or not os.environ.get("AAC_LIB"):
+        L.aac_clip_last_error.restype = ctypes.c_char_p
+        L.aac_clip_partials.argtypes = [ctypes.c_int64]
+        L.aac_clip_partials.restype = ctypes.c_int64
+        L.aac_clip_sumsq.argtypes = [ctypes.POINTER(ClipJob), i32, i32, vp]
+        L.aac_adam_flat_clip.argtypes = [ctypes.POINTER(ClipJob), i32, i32, vp]
     for name in EXPORTS:
         if os.environ.get("AAC_LIB") and not hasattr(L, name):
             continue          # an A/B experiment build of an earlier revision

@@ -32,6 +32,32 @@ __device__ __forceinline__ double adam_bc2_sqrt(double b2, int t) {
     return sqrt(bc2);
 }
 
+// One element's Adam step on gradient gi, for kernels that keep the expression outside their loop
+// (aac_clip.hip): the float form is adam_kernel's (aac_learn.hip; torch's lerp / addcmul / addcdiv
+// order), the double form adam64_kernel's (aac_uam_learn.hip), operation for operation.
+__device__ __forceinline__ void adam_elem(float &p, float &m, float &v, float gi, float b1, float b2, float eps,
+                                          float step_size, float bc2s) {
+    const float w1 = (float)(1.0 - (double)b1), w2 = (float)(1.0 - (double)b2);
+    float mi = m;
+    mi = mi + w1 * (gi - mi);
+    float vi = v * b2;
+    vi = vi + w2 * (gi * gi);
+    const float den = sqrtf(vi) / bc2s + eps;
+    p = p + (-step_size) * (mi / den);
+    m = mi;
+    v = vi;
+}
+
+__device__ __forceinline__ void adam_elem(double &p, double &m, double &v, double gi, double b1, double b2,
+                                          double eps, double step_size, double bc2s) {
+    const double mi = b1 * m + (1.0 - b1) * gi;
+    const double vi = b2 * v + (1.0 - b2) * gi * gi;
+    const double den = sqrt(vi) / bc2s + eps;
+    p = p - step_size * mi / den;
+    m = mi;
+    v = vi;
+}
+
 // Every thread of the workgroup calls this exactly once, outside any divergent branch or loop (it
 // holds the workgroup barrier), after issuing its first loads.  sh: two T in LDS.  The branches are
 // wave-uniform.  The sched_barrier keeps the compiler from sinking those loads below the fp64 block.

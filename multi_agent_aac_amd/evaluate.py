@@ -15,6 +15,7 @@ With several ranks each rank evaluates its own envs; the results are not combine
 """
 import torch
 
+from . import graphs as _graphs
 from . import trainer as _trainer
 from .stats import EpisodeStats
 
@@ -137,7 +138,7 @@ class Evaluator:
         graphs = []
         for p in (0, 1):
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
+            with _graphs.capture(g):
                 step(p)
             graphs.append(g)
         return graphs

@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from . import _native, ops, parallel
+from . import clip as _clip
 
 vp = ctypes.c_void_p
 i32 = ctypes.c_int32
@@ -650,6 +651,9 @@ class FusedUpdate:
         self.mon = getattr(model, "monitor", None)
         if self.mon is not None and model.world > 1:
             raise ValueError("FusedUpdate: the learner monitor supports world == 1 only")
+        # gradient clipping (clip.GradClip) set on the model, or None: each clipped network's Adam
+        # launches become aac_clip_sumsq + aac_adam_flat_clip
+        self.clip = getattr(model, "clip", None)
         N, D0, K = model.n_agents, model.D0, model.n_agents - 1
         self.N, self.D0, self.K, self.Din = N, D0, K, D0 + 2
         dev = model.device
@@ -770,30 +774,60 @@ class FusedUpdate:
     def _adam(self, opt, flat, gpart, ns, step_add):
         """world == 1: the Adam step sums the split-K partial copies itself.  world > 1: the partial
         copies are summed into the shared gradient buffer, all-reduced (SUM) and the Adam launch
-        applies the 1 / world."""
+        applies the 1 / world.  With gradient clipping on for the network (``model.set_grad_clip``) the
+        Adam launch becomes aac_clip_sumsq + aac_adam_flat_clip: at world == 1 the first sums the copies
+        (and writes ``flat.grad``), at world > 1 it reads the all-reduced sum with gscale = 1 / world."""
         m = self.m
         critic = opt is m.critic_optimizer
+        st = self._clip_step(opt, flat, gpart, ns, step_add)
         if m.world == 1:
             col = step_add - 1
-            return ([lambda: adam_sum(opt, gpart, ns, step_add, grad_out=flat.grad)]
+            return (([lambda: adam_sum(opt, gpart, ns, step_add, grad_out=flat.grad)] if st is None
+                     else [st.sumsq, st.adam])
                     + self._mon_vec(col if critic else None, None if critic else col))
         return [lambda: sum_partials(flat.grad, gpart, ns),
-                Collective(lambda: m._allreduce_grads(critic=critic, actor=not critic)),
-                lambda: adam_at(opt, step_add, 1.0 / m.world)]
+                Collective(lambda: m._allreduce_grads(critic=critic, actor=not critic))] + self._adam_reduced(opt, st, step_add)
+
+    def _clip_step(self, opt, flat, gpart, ns, step_add):
+        """The clip.Step of this Adam boundary, or None where the network is not clipped."""
+        m = self.m
+        net = 0 if opt is m.critic_optimizer else 1
+        if self.clip is None or not self.clip.on(net):
+            return None
+        if m.world > 1:
+            return self.clip.step(net, opt, flat.grad, step_add=step_add, gscale=1.0 / m.world)
+        from .monitor import adam4_order
+        return self.clip.step(net, opt, gpart, nsplit=ns, gstride=gpart.shape[-1], order=adam4_order(gpart, ns),
+                              grad_out=flat.grad, step_add=step_add)
+
+    def _adam_reduced(self, opt, st, step_add):
+        """world > 1: the Adam launch(es) on the all-reduced gradient sum."""
+        if st is None:
+            return [lambda: adam_at(opt, step_add, 1.0 / self.m.world)]
+        return [st.sumsq, st.adam]
 
     def _adam_pair(self, i_critic, i_actor):
         """Critic Adam step i_critic + 1 and actor Adam step i_actor + 1 as one launch (or two); at
-        world > 1 behind ONE all-reduce of both gradients (contiguous in MADDPG._share_grads)."""
+        world > 1 behind ONE all-reduce of both gradients (contiguous in MADDPG._share_grads).  With
+        both networks clipped: one two-job aac_clip_sumsq and one two-job aac_adam_flat_clip launch."""
         m = self.m
         ca = (m.critic_optimizer, self.gc, self.SPLIT_CRITIC, i_critic + 1, m.fc.grad)
         aa = (m.actor_optimizer, self.ga, self.SPLIT_ACTOR, i_actor + 1, m.fa.grad)
+        sc = self._clip_step(ca[0], m.fc, *ca[1:4])
+        sa = self._clip_step(aa[0], m.fa, *aa[1:4])
+        both = sc is not None and sa is not None
         if m.world > 1:
-            gs = 1.0 / m.world
             return [lambda: sum_partials(m.fa.grad, self.ga, self.SPLIT_ACTOR),
                     lambda: sum_partials(m.fc.grad, self.gc, self.SPLIT_CRITIC),
-                    Collective(lambda: m._allreduce_grads(critic=True, actor=True)),
-                    lambda: adam_at(ca[0], ca[3], gs), lambda: adam_at(aa[0], aa[3], gs)]
+                    Collective(lambda: m._allreduce_grads(critic=True, actor=True))] + (
+                _clip.pair(sc, sa) if both else
+                self._adam_reduced(ca[0], sc, ca[3]) + self._adam_reduced(aa[0], sa, aa[3]))
         mon = self._mon_vec(i_critic, i_actor)
+        if both:
+            return _clip.pair(sc, sa) + mon
+        if sc is not None or sa is not None:     # one network clipped: its two launches, the other's own
+            return ([sc.sumsq, sc.adam] if sc is not None else [lambda: adam_sum(*ca[:4], grad_out=ca[4])]) + (
+                [sa.sumsq, sa.adam] if sa is not None else [lambda: adam_sum(*aa[:4], grad_out=aa[4])]) + mon
         if adam_pair_ok(self.gc, self.ga):
             return [lambda: adam_sum_pair(ca, aa)] + mon
         return [lambda: adam_sum(*ca[:4], grad_out=ca[4]), lambda: adam_sum(*aa[:4], grad_out=aa[4])] + mon
@@ -947,21 +981,21 @@ class FusedUpdate:
         m, N = self.m, self.N
         SA, SC = self.SPLIT_ACTOR, self.SPLIT_CRITIC
         copt, aopt = m.critic_optimizer, m.actor_optimizer
-        gs = 1.0 / m.world          # the collectives SUM; each Adam launch applies the 1 / world
+        # (the collectives SUM; each Adam launch applies the 1 / world)
         red_c = lambda: sum_partials(m.fc.grad, self.gc, SC)      # noqa: E731
         red_a = lambda: sum_partials(m.fa.grad, self.ga, SA)      # noqa: E731
         L = self._critic_step(0, A, C, self.cbuf[0], fuse_actor_fwd=False)
-        L += [red_c, Collective(lambda: m._allreduce_grads(critic=True, actor=False)), lambda: adam_at(copt, 1, gs)]
+        at = lambda opt, flat, k: self._adam_reduced(opt, self._clip_step(opt, flat, None, 1, k), k)    # noqa: E731
+        L += [red_c, Collective(lambda: m._allreduce_grads(critic=True, actor=False))] + at(copt, m.fc, 1)
         segs = [L]
         for i in range(N):
             L = self._actor_fwd_launches(i, A) + self._actor_step(i, A, C)
             if i + 1 < N:
                 L += self._critic_step(i + 1, A, C, self.cbuf[1], fuse_actor_fwd=False)
-                L += [red_a, red_c, Collective(lambda: m._allreduce_grads(critic=True, actor=True)),
-                      lambda i=i: adam_at(copt, i + 2, gs), lambda i=i: adam_at(aopt, i + 1, gs)]
+                L += [red_a, red_c, Collective(lambda: m._allreduce_grads(critic=True, actor=True))]
+                L += at(copt, m.fc, i + 2) + at(aopt, m.fa, i + 1)
             else:
-                L += [red_a, Collective(lambda: m._allreduce_grads(critic=False, actor=True)),
-                      lambda i=i: adam_at(aopt, i + 1, gs)]
+                L += [red_a, Collective(lambda: m._allreduce_grads(critic=False, actor=True))] + at(aopt, m.fa, i + 1)
             segs.append(L)
         return segs
 

@@ -36,6 +36,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from . import graphs as _graphs
 from . import fused, ops, parallel, trace
 from .fused import RELU, TANH, Collective, gemm_launches, prob, ptr
 from .memory import DeviceReplay, Experience, ReplayMemory
@@ -355,7 +356,13 @@ class GruUpdate:
         L = []
         if m.world > 1:     # SUM over the ranks; the Adam launch applies the 1 / world
             L.append(Collective(lambda: m._allreduce(flat)))
-        L.append(lambda: fused.adam_at(opt, 1, 1.0 / m.world))
+        net = 0 if flat is m.fc else 1
+        if m.clip is not None and m.clip.on(net):
+            # the norm of each agent's segment of the (mean) gradient, then the Adam step on g * coef
+            st = m.clip.step(net, opt, flat.grad, step_add=1, gscale=1.0 / m.world)
+            L += [st.sumsq, st.adam]
+        else:
+            L.append(lambda: fused.adam_at(opt, 1, 1.0 / m.world))
         if self.mon is not None:
             # the norms of the N per-agent segments of the flat gradient the Adam launch just read
             # (one copy, agent-major) and of the parameters it wrote: column i = agent i
@@ -564,7 +571,7 @@ class MADDPG:
 
     def __init__(self, actor_dim, critic_dim, dim_act, actor_hidden_state_size=H, gru_history_length=10, n_agents=8,
                  args=None, cr_lr=1e-3, ac_lr=1e-3, gamma=0.95, tau=0.01, device=None, seed=None, memory_length=None,
-                 batch_size=None, process_group=None, own_width=None):
+                 batch_size=None, process_group=None, own_width=None, grad_clip=None):
         """own_width: the env's own-observation row width the act / replay rows use: 6 for the WGRU
         env variant (``BatchedEnv(variant="wgru")``, WGRU/env:990), default 6 + 4 (N - 1) (the ATT
         env's rows, of which the networks read the first actor_dim[0])."""
@@ -611,6 +618,9 @@ class MADDPG:
         self._graph_B = None
         self._last_src = None
         self.steps_done = 0
+        self.clip = None
+        if grad_clip is not None:
+            self.set_grad_clip(grad_clip)
 
     # ------------------------------------------------------------------ batched API
     def attach_replay(self, capacity, seed=0):
@@ -660,6 +670,25 @@ class MADDPG:
         self._plans = {}
         self._graph = None
 
+    def set_grad_clip(self, value):
+        """Clip each agent network's gradient norm ahead of its Adam step, as the reference's
+        ``clip_grad_norm_(net.parameters(), max_norm)`` per agent critic / actor: None (off), one bound for
+        both kinds, or a (critic, actor) pair whose entries may be None or ``float("inf")``.  The units are
+        the N agent-major segments of ``fc`` / ``fa``.  Cached plans and the captured graph are dropped,
+        and the record starts again."""
+        from . import clip
+        self.clip = clip.make(value, self.n_agents, self.device)
+        self._plans = {}
+        self._graph = None
+
+    def clip_record(self, clear=False):
+        """The clipping record as plain numpy (synchronises): {field: {"critic": [N], "actor": [N]}} for
+        the fields ``steps``, ``clipped``, ``nonfinite``, ``last_norm``, ``last_coef``,
+        ``max_norm_seen``; entry i is agent i's network.  Per rank, not checkpointed."""
+        if self.clip is None:
+            raise ValueError("clip_record: gradient clipping is off (grad_clip=None)")
+        return self.clip.read(clear)
+
     def _plan(self, B, rep=None):
         if rep is None:
             rep = self.replay if self.replay is not None else self.memory.dev
@@ -674,6 +703,8 @@ class MADDPG:
         ts += self.actor_optimizer.state() + self.critic_optimizer.state()
         if self.monitor is not None:      # the capture's warm-up updates leave no record
             ts += list(self.monitor.tensors().values())
+        if self.clip is not None:
+            ts.append(self.clip.record)
         return ts, [t.clone() for t in ts]
 
     def capture(self, B, warmup=2):
@@ -691,7 +722,7 @@ class MADDPG:
         graphs = []
         for seg in segs:
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
+            with _graphs.capture(g):
                 for op in seg:
                     op()
             graphs.append(g)

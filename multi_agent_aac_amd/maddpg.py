@@ -20,6 +20,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from . import graphs as _graphs
+from . import clip as _clip
 from . import fused, ops, parallel, trace
 from .memory import DeviceReplay, ReplayMemory
 from .networks import ActorNetwork_ATT_TwoPortion, CriticCombine, FlatParams
@@ -33,12 +35,17 @@ class _Adam:
         self.exp_avg = torch.zeros_like(flat.data)
         self.exp_avg_sq = torch.zeros_like(flat.data)
         self.step_t = torch.zeros(1, dtype=torch.int32, device=flat.data.device)
+        self.clip_step = None      # clip.Step on flat.grad while the model clips this network (set_grad_clip)
 
     def zero_grad(self):
         self.flat.zero_grad()
 
     def step(self):
         self.step_t.add_(1)
+        if self.clip_step is not None:      # the norm of flat.grad, then the Adam step on the clipped gradient
+            self.clip_step.sumsq()
+            self.clip_step.adam()
+            return
         ops.adam_flat(self.flat.data, self.flat.grad, self.exp_avg, self.exp_avg_sq, self.step_t, self.lr,
                       self.betas[0], self.betas[1], self.eps)
 
@@ -58,7 +65,7 @@ class MADDPG:
     def __init__(self, actor_dim, critic_dim, dim_act, actor_hidden_state_size=64, gru_history_length=10,
                  n_agents=5, args=None, cr_lr=1e-3, ac_lr=1e-3, gamma=0.95, tau=0.01,
                  full_observable_critic_flag=True, device=None, seed=None, memory_length=None, batch_size=None,
-                 process_group=None, blas="cublas", fused=True):
+                 process_group=None, blas="cublas", fused=True, grad_clip=None):
         self.args = args
         self.fused = bool(fused)     # fused HIP learner (fused.py); False = autograd over layers.py
         self.device = torch.device(device) if device is not None else torch.device("cuda")
@@ -110,6 +117,9 @@ class MADDPG:
         self._fplans = {}
         self._infer = None
         self.monitor = None
+        self.clip = None
+        if grad_clip is not None:
+            self.set_grad_clip(grad_clip)
 
     # ------------------------------------------------------------------ batched API
     def attach_replay(self, capacity, seed=0):
@@ -214,6 +224,27 @@ class MADDPG:
         self._fplans = {}
         self._graph = None
 
+    def set_grad_clip(self, value):
+        """Clip each network's gradient norm ahead of its Adam step, as the reference's
+        ``clip_grad_norm_(net.parameters(), max_norm)`` (ATT/maddpg:187, :205-206): None (off), one bound
+        for both networks, or a (critic, actor) pair whose entries may be None or ``float("inf")``.  The
+        unit is a whole network (``fc`` / ``fa``), once per gradient iteration.  Cached plans and the
+        captured graph are dropped, and the record starts again."""
+        self.clip = _clip.make(value, 1, self.device)
+        for net, opt in enumerate((self.critic_optimizer, self.actor_optimizer)):
+            on = self.clip is not None and self.clip.on(net)
+            opt.clip_step = self.clip.step(net, opt, opt.flat.grad) if on else None
+        self._fplans = {}
+        self._graph = None
+
+    def clip_record(self, clear=False):
+        """The clipping record as plain numpy (synchronises): {field: {"critic": [1], "actor": [1]}} for
+        the fields ``steps``, ``clipped``, ``nonfinite``, ``last_norm``, ``last_coef``,
+        ``max_norm_seen``.  Per rank, not checkpointed."""
+        if self.clip is None:
+            raise ValueError("clip_record: gradient clipping is off (grad_clip=None)")
+        return self.clip.read(clear)
+
     def _update_core(self, B, idx_list=None, rep=None, soft=True, freeze_actor=False):
         if rep is None:
             rep = self.replay if self.replay is not None else self.memory.dev
@@ -244,6 +275,8 @@ class MADDPG:
         ts += self.actor_optimizer.state() + self.critic_optimizer.state()
         if self.monitor is not None:      # the capture's warm-up updates leave no record
             ts += list(self.monitor.tensors().values())
+        if self.clip is not None:
+            ts.append(self.clip.record)
         return ts, [t.clone() for t in ts]
 
     def capture(self, B, warmup=2):
@@ -269,7 +302,7 @@ class MADDPG:
             graphs = []
             for seg in segs:
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
+                with _graphs.capture(g):
                     for op in seg:
                         op()
                 graphs.append(g)
@@ -280,14 +313,14 @@ class MADDPG:
             fu = self._fused_plan(B)
             side = torch.cuda.Stream()
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
+            with _graphs.capture(g):
                 fu.run_streams(side)
             self._graph_stats = fu
             self._graph = g
             self._side = side
         else:
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
+            with _graphs.capture(g):
                 self._graph_stats = self._update_core(B)
             self._graph = g
         for t, v in zip(ts, saved):

@@ -29,6 +29,7 @@ import os
 
 import torch
 
+from . import graphs as _graphs
 from . import trace
 
 NO_GRAPH = False
@@ -121,6 +122,8 @@ class CheckpointMixin:
         out = self.stats.read() if self.stats is not None else None
         if getattr(self, "ledger", None) is not None:      # with a ledger: the statistics plus its report
             out = dict(out or {}, terms=self.ledger.read())
+        if getattr(self.model, "clip", None) is not None:  # with gradient clipping: the model's clip record
+            out = dict(out or {}, clip=self.model.clip_record())
         return out
 
     def terms(self):
@@ -153,10 +156,15 @@ class Trainer(CheckpointMixin):
     (``terms.RewardLedger``): one small launch after the stats launch position of every env step, eager
     or inside the whole-step graphs; ``terms()`` reads them.  Off (the default) the env launches and the
     launch sequence are unchanged and ``self.ledger`` is None.  The ledger is not checkpointed: a
-    resumed run starts an empty one."""
+    resumed run starts an empty one.
+
+    ``grad_clip`` (None, a bound, or a (critic, actor) pair) is the model's ``set_grad_clip``: each clipped
+    network's Adam launches carry the reference's ``clip_grad_norm_``, eager or captured, and ``finish()``
+    returns the record under ``"clip"``.  Off (the default) the launch lists are unchanged.  The record is
+    not checkpointed."""
 
     def __init__(self, E, N, B, memory, radar, seed, pg=None, model="att", maps=1, stats=False, monitor=False,
-                 terms=False):
+                 terms=False, grad_clip=None):
         from . import world
         from .env import BatchedEnv
         from .maddpg import MADDPG
@@ -178,14 +186,15 @@ class Trainer(CheckpointMixin):
             from . import gru
             # WGRU/ma_main:380-389: actor_dim = critic_dim = [6, 18, 6], 64 hidden units
             self.model = gru.MADDPG([6, 18, 6], [6, 18, 6], 2, 64, 10, n_agents=N, seed=777, batch_size=B,
-                                    memory_length=memory, process_group=pg, own_width=self.env.D0)
+                                    memory_length=memory, process_group=pg, own_width=self.env.D0,
+                                    grad_clip=grad_clip)
             # hidden states as a ping-pong pair: act reads h[k] and writes the next hidden into h[1 - k]
             # (one act plan per buffer set, no copies)
             self.hp = [torch.zeros(E, N, 64, device="cuda"), torch.zeros(E, N, 64, device="cuda")]
             self.h = self.hp[0]
         else:
             self.model = MADDPG([D0, 18, 6], [D0, 18, 6], 2, n_agents=N, seed=777, batch_size=B,
-                                memory_length=memory, process_group=pg)
+                                memory_length=memory, process_group=pg, grad_clip=grad_clip)
         self.model.noise_seed = 99 + seed
         self.replay = self.model.attach_replay(memory, seed=seed)
         self.cur = self.env.alloc_buffers()
@@ -260,7 +269,7 @@ class Trainer(CheckpointMixin):
         else:
             self.model._plan(self.B)
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
+        with _graphs.capture(g):
             for k in range(steps):
                 self._step_body(p ^ (k & 1), side)
         self.replay.pos, self.replay.size = saved
@@ -268,13 +277,14 @@ class Trainer(CheckpointMixin):
 
     def _graphs_current(self):
         gen = getattr(self.env, "bank_generation", 0)
-        mon = self.model.monitor
+        mon, clp = self.model.monitor, self.model.clip
         if (self._sg or getattr(self, "_sg2", None)) and (getattr(self, "_sg_bank_gen", gen) != gen
-                                                          or getattr(self, "_sg_mon", mon) is not mon):
-            # the env's OD bank / seed changed, or a learner monitor was attached / detached (new update
-            # plans), under the captured graphs
+                                                          or getattr(self, "_sg_mon", mon) is not mon
+                                                          or getattr(self, "_sg_clip", clp) is not clp):
+            # the env's OD bank / seed changed, or a learner monitor was attached / detached or the
+            # gradient clipping reset (new update plans), under the captured graphs
             self._sg, self._sg2 = {}, {}
-        self._sg_bank_gen, self._sg_mon = gen, mon
+        self._sg_bank_gen, self._sg_mon, self._sg_clip = gen, mon, clp
         if self.gru and not self._sg and not getattr(self, "_sg2", None):
             # (re)capture: the hidden-state pair's offset against the buffer parity, as of now
             p = 0 if self.cur is self.bufs[0] else 1
@@ -443,8 +453,10 @@ class UamTrainer(CheckpointMixin):
     stream (the reset touches neither the terms nor ``env_done``).  Off (the default) the launches are
     unchanged and ``self.ledger`` is None."""
 
-    def __init__(self, E, N, B, memory, seed, pg=None, stats=False, monitor=False, terms=False):
+    def __init__(self, E, N, B, memory, seed, pg=None, stats=False, monitor=False, terms=False, grad_clip=None):
         from . import uam, uam_learner
+        if grad_clip is not None:      # not built for the float64 UAM learner: NotImplementedError
+            uam_learner.unsupported_grad_clip()
         self.E, self.N, self.B = E, N, B
         self.gru = False
         # BASELINE.md config 5: tdCPA outputs live (tcpa / dcpa per neighbour, conflict counts)
@@ -511,7 +523,7 @@ class UamTrainer(CheckpointMixin):
         side = torch.cuda.Stream() if UAM_OVERLAP_RESET else None
         self.model.fused(self.B, self.replay)        # built outside the capture
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
+        with _graphs.capture(g):
             for k in range(steps):
                 self._step_body(p ^ (k & 1), side)
         self.replay.pos, self.replay.size = saved

@@ -32,6 +32,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from . import graphs as _graphs
 from . import ops, parallel, trace, uam
 
 F64 = torch.float64
@@ -79,6 +80,14 @@ def noise_scale(episode, eps_end, start_scale=1, end_scale=0):
     slope = (end_scale - start_scale) / (eps_end - 1)
     ep = episode.to(F64)
     return torch.where(ep <= eps_end, start_scale + slope * (ep - 1), torch.full_like(ep, float(end_scale)))
+
+
+def unsupported_grad_clip():
+    """Gradient clipping (``grad_clip`` / ``set_grad_clip`` of the ATT and GRU learners) is not wired into
+    the float64 UAM plan.  The double instantiations of aac_clip_sumsq / aac_adam_flat_clip are built
+    and tested; the follow-up is putting them where FusedUamUpdate calls aac_adam64_sum_scaled."""
+    raise NotImplementedError("grad_clip: the float64 UAM learner does not clip yet -- follow-up: the double "
+                              "aac_clip_sumsq + aac_adam_flat_clip launches in FusedUamUpdate's Adam boundaries")
 
 
 class UamReplay:
@@ -492,7 +501,7 @@ class FusedUamUpdate:
         graphs = []
         for seg in segs:
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
+            with _graphs.capture(g):
                 for f in seg:
                     f()
             graphs.append(g)
@@ -688,7 +697,7 @@ class MADDPG:
                 self._sampled_core(rep, B)
         torch.cuda.current_stream().wait_stream(s)
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
+        with _graphs.capture(g):
             self._graph_out = self._sampled_core(rep, B)
         for t, v in zip(self._state_tensors(rep), snap):
             t.copy_(v)
@@ -779,6 +788,10 @@ class MADDPG:
         self.monitor = mon
         self._fu = None
         self._graph = None
+
+    def set_grad_clip(self, value):
+        """Not built for this learner (``unsupported_grad_clip``)."""
+        unsupported_grad_clip()
 
     def invalidate_graphs(self):
         """Drop every captured update graph (a checkpoint load changed a seed the graphs bake in)."""
