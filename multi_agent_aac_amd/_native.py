@@ -25,6 +25,7 @@ EXPORTS = (
     "aac_env_set_terms_buffer", "aac_terms_last_error", "aac_terms_names", "aac_terms_accumulate", "aac_terms_reduce",
     "aac_terms_record",
     "aac_clip_last_error", "aac_clip_partials", "aac_clip_sumsq", "aac_adam_flat_clip",
+    "aac_env_probe",
 )
 
 vp = ctypes.c_void_p
@@ -121,6 +122,10 @@ class ClipJob(ctypes.Structure):           # aac_clip_job (include/aac_clip.h)
                [(n, ctypes.c_double) for n in ("gscale", "max_norm", "lr", "beta1", "beta2", "eps")]
 
 
+class ProbeOut(ctypes.Structure):          # aac_probe_out (include/aac_probe.h)
+    _fields_ = [(n, vp) for n in ("dist", "point", "end", "kind", "id")]
+
+
 _lib = None
 
 
@@ -179,6 +184,8 @@ def lib():
         L.aac_clip_partials.restype = ctypes.c_int64
         L.aac_clip_sumsq.argtypes = [ctypes.POINTER(ClipJob), i32, i32, vp]
         L.aac_adam_flat_clip.argtypes = [ctypes.POINTER(ClipJob), i32, i32, vp]
+    if hasattr(L, "aac_env_probe") or not os.environ.get("AAC_LIB"):
+        L.aac_env_probe.argtypes = [vp, vp, vp, ctypes.c_int64, vp, ctypes.POINTER(ProbeOut), vp]
     for name in EXPORTS:
         if os.environ.get("AAC_LIB") and not hasattr(L, name):
             continue          # an A/B experiment build of an earlier revision

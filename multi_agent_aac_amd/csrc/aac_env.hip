@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/aac_env.h"
+#include "../../include/aac_probe.h"
 #include "../../include/aac_terms.h"
 #include "aac_geom.h"
 #include "aac_wave.h"
@@ -1602,6 +1603,125 @@ __global__ void __launch_bounds__(1024) env_compact_kernel(const uint8_t *__rest
     aacw::compact_flags(mask, E, rlist);
 }
 
+// ------------------------------------------------------------------------------- radar probes
+// include/aac_probe.h: per (row, agent, ray) the radar value in double, what the ray ended on and where.
+// The candidates and comparisons are radar_ray's / radar_obstacles' (the drone pre-filter, the cells of the
+// segment's box behind the line filter, the four bound lines), every threshold-band case decided
+// exactly in place (mode 2, as radar_ray_exact does: nothing goes to the handle's band list), so the
+// value is the one the step / reset launch and its band fix leave in ``radar``.
+struct ProbeArgs {
+    int64_t M;
+    int N, mode, gw, gh, n_maps;
+    double pb, rlen, gx0, gy0, bound[4];
+    const double2 *pos;                    // [M][N]
+    const int32_t *map_idx;                // [M], null: map 0
+    const uint8_t *sel;                    // [M], null: all rows
+    const uint8_t *occ;                    // the handle's map stack (global memory: read through L2)
+    double *dist;
+    double2 *point, *end;                  // end may be null
+    uint8_t *kind;
+    int32_t *id;
+};
+static_assert(sizeof(aac_probe_out) == AAC_PROBE_OUT_BYTES, "the header's constant for bindings");
+// a workgroup takes BLOCK consecutive work items of the (row, agent, ray) index space: they span at most
+// 255 / (18 N) + 2 rows, i.e. fewer than 15 + 2 N agents
+#define PROBE_STAGE (2 * BLOCK + 16)
+
+struct ProbeHit {
+    double d, x, y;
+    int kind, id;
+};
+
+// the tie rule: the smaller distance, and among bit-equal distances the lowest (kind, id) -- independent
+// of the order the candidates come in
+__device__ inline void probe_take(ProbeHit &b, double d, int kind, int id, double x, double y) {
+    if (d < b.d || (d == b.d && (kind < b.kind || (kind == b.kind && id < b.id)))) b = ProbeHit{d, x, y, kind, id};
+}
+
+__global__ void __launch_bounds__(BLOCK) radar_probe_kernel(ProbeArgs P) {
+    __shared__ double2 s_pos[PROBE_STAGE];
+    const int N = P.N;
+    const int per_row = N * NRAY;
+    const int64_t total = P.M * per_row;
+    const int64_t w0 = (int64_t)blockIdx.x * BLOCK;
+    const int64_t w1 = w0 + BLOCK < total ? w0 + BLOCK : total;        // this workgroup's items [w0, w1)
+    const int64_t row0 = w0 / per_row;
+    const int rows = (int)((w1 - 1) / per_row - row0) + 1;
+    for (int k = threadIdx.x; k < rows * N; k += BLOCK) s_pos[k] = P.pos[row0 * N + k];
+    __syncthreads();
+    const double pb = P.pb;
+    const int64_t wg = w0 + threadIdx.x;
+    if (wg < w1) {
+        const int w = (int)(wg - row0 * per_row);
+        const int la = w / NRAY, r = w - la * NRAY;
+        const int le = la / N, i = la - le * N;
+        const int64_t row = row0 + le;
+        if (P.sel && !P.sel[row]) return;
+        int mi = P.map_idx ? P.map_idx[row] : 0;
+        mi = mi < 0 ? 0 : (mi > P.n_maps - 1 ? P.n_maps - 1 : mi);
+        const uint8_t *occ = P.occ + (size_t)mi * P.gw * P.gh;
+        const double2 *pos = s_pos + le * N;
+        const double px = pos[i].x, py = pos[i].y;
+        const double ex = px + P.rlen * c_tab.ray_c[r], ey = py + P.rlen * c_tab.ray_s[r];
+        const double len = gdist(ex, ey, px, py);
+        const double ddx = ex - px, ddy = ey - py;
+        const double L2 = ddx * ddx + ddy * ddy;
+        bool band = false;       // unused: mode 2 decides
+        ProbeHit b{INFINITY, ex, ey, AAC_PROBE_NONE, -1};
+        if (P.mode != AAC_RADAR_OBSTACLES) {
+            // radar_ray's pre-filter (closest point of the segment within pb + 1e-6 of the neighbour)
+            const double reach2 = (pb + 1e-6) * (pb + 1e-6);
+            const double inv = 1.0 / L2;
+            for (int j = 0; j < N; ++j) {
+                const double2 q = pos[j];
+                const double wx = q.x - px, wy = q.y - py;
+                double tt = (wx * ddx + wy * ddy) * inv;
+                tt = tt < 0.0 ? 0.0 : (tt > 1.0 ? 1.0 : tt);
+                const double qx = tt * ddx - wx, qy = tt * ddy - wy;
+                if (j == i || !(qx * qx + qy * qy <= reach2)) continue;
+                double t;
+                if (!ray_poly_entry<1>(px, py, ex, ey, q.x, q.y, pb, t, band, 2)) continue;
+                const double ix = px + t * (ex - px), iy = py + t * (ey - py);
+                probe_take(b, gdist(ix, iy, px, py), AAC_PROBE_DRONE, j, ix, iy);
+            }
+        }
+        if (P.mode != AAC_RADAR_DRONES) {
+            double d, hx, hy;
+            int i0 = (int)floor((fmin(px, ex) - 5.0 - P.gx0) * 0.1), i1 = (int)ceil((fmax(px, ex) + 5.0 - P.gx0) * 0.1);
+            int j0 = (int)floor((fmin(py, ey) - 5.0 - P.gy0) * 0.1), j1 = (int)ceil((fmax(py, ey) + 5.0 - P.gy0) * 0.1);
+            i0 = i0 < 0 ? 0 : i0;
+            j0 = j0 < 0 ? 0 : j0;
+            i1 = i1 > P.gw - 1 ? P.gw - 1 : i1;
+            j1 = j1 > P.gh - 1 ? P.gh - 1 : j1;
+            const double reach = 5.0 * (fabs(ddx) + fabs(ddy)) * (1.0 + 1e-9) + 1e-12;     // radar_obstacles' line filter
+            for (int ci = i0; ci <= i1; ++ci)
+                for (int cj = j0; cj <= j1; ++cj) {
+                    if (!occ[ci * P.gh + cj]) continue;
+                    const double qx = P.gx0 + 10.0 * ci, qy = P.gy0 + 10.0 * cj;
+                    const double wx = qx - px, wy = qy - py;
+                    const double cr = wx * ddy - wy * ddx, al = wx * ddx + wy * ddy;
+                    if (fabs(cr) > reach || al < -reach || al > L2 + reach) continue;
+                    if (ray_square_pt<1>(px, py, ex, ey, qx - 5.0, qx + 5.0, qy - 5.0, qy + 5.0, d, hx, hy, band, 2) &&
+                        d <= len)
+                        probe_take(b, d, AAC_PROBE_CELL, ci * P.gh + cj, hx, hy);
+                }
+            if (ray_vline_pt(px, py, ex, ey, P.bound[0], d, hx, hy) && d < len) probe_take(b, d, AAC_PROBE_BOUND, 0, hx, hy);
+            if (ray_vline_pt(px, py, ex, ey, P.bound[1], d, hx, hy) && d < len) probe_take(b, d, AAC_PROBE_BOUND, 1, hx, hy);
+            if (ray_hline_pt(px, py, ex, ey, P.bound[2], d, hx, hy) && d < len) probe_take(b, d, AAC_PROBE_BOUND, 2, hx, hy);
+            if (ray_hline_pt(px, py, ex, ey, P.bound[3], d, hx, hy) && d < len) probe_take(b, d, AAC_PROBE_BOUND, 3, hx, hy);
+        }
+        // nothing hit, or (combined) only a drone whose distance rounds above len while the obstacle side
+        // kept len: the value is len and no candidate attains it
+        if (b.kind == AAC_PROBE_NONE || (P.mode == AAC_RADAR_COMBINED && b.d > len)) b = ProbeHit{len, ex, ey, AAC_PROBE_NONE, -1};
+        const size_t o = ((size_t)row * N + i) * NRAY + r;
+        P.dist[o] = b.d;
+        P.point[o] = make_double2(b.x, b.y);
+        if (P.end) P.end[o] = make_double2(ex, ey);
+        P.kind[o] = (uint8_t)b.kind;
+        P.id[o] = b.id;
+    }
+}
+
 // ------------------------------------------------------------------------------ host side
 thread_local std::string g_err;
 // Auto-reset over the packed list of done envs: -1 (default) per variant -- off for the ATT env, where
@@ -2157,6 +2277,43 @@ int aac_env_record(aac_env *h, const aac_record_state *state, const aac_record_s
     p.map_idx = h->map_idx;
     p.heading = p.clouds = nullptr;
     if (int rc = aac_record(state, &p, stream)) return fail(rc, aac_record_last_error());
+    return AAC_OK;
+}
+
+int aac_env_probe(aac_env *h, const double *pos_dev, const int32_t *map_idx_dev, int64_t M, const uint8_t *sel_dev,
+                  const aac_probe_out *out, void *stream) {
+    if (!h || !out) return fail(AAC_E_INVALID, "null argument");
+    if (!out->dist || !out->point || !out->kind || !out->id) return fail(AAC_E_INVALID, "probe: dist, point, kind, id required");
+    if ((reinterpret_cast<uintptr_t>(out->point) | reinterpret_cast<uintptr_t>(out->end) |
+         reinterpret_cast<uintptr_t>(pos_dev)) & 15)
+        return fail(AAC_E_INVALID, "probe: pos, point and end must be 16-byte aligned");
+    const aac_env_cfg &c = h->cfg;
+    if (!pos_dev && M != c.E) return fail(AAC_E_INVALID, "probe: the live state has E rows");
+    ProbeArgs P;
+    P.M = M;
+    P.N = c.N;
+    P.mode = c.radar_mode;
+    P.gw = c.grid_w;
+    P.gh = c.grid_h;
+    P.n_maps = c.n_maps;
+    const int64_t blocks = (M * c.N * NRAY + BLOCK - 1) / BLOCK;
+    if (M < 1 || M > (int64_t)1 << 40 || blocks > 0x7fffffff) return fail(AAC_E_INVALID, "probe: M out of range");
+    P.pb = c.pB;
+    P.rlen = c.radar_len;
+    P.gx0 = std::ceil(c.bound[0] / c.cell) * c.cell;
+    P.gy0 = std::ceil(c.bound[2] / c.cell) * c.cell;
+    for (int k = 0; k < 4; ++k) P.bound[k] = c.bound[k];
+    P.pos = pos_dev ? reinterpret_cast<const double2 *>(pos_dev) : h->pos;
+    P.map_idx = pos_dev ? map_idx_dev : h->map_idx;
+    P.sel = sel_dev;
+    P.occ = h->occ;
+    P.dist = out->dist;
+    P.point = reinterpret_cast<double2 *>(out->point);
+    P.end = reinterpret_cast<double2 *>(out->end);
+    P.kind = out->kind;
+    P.id = out->id;
+    hipLaunchKernelGGL(radar_probe_kernel, dim3((unsigned)blocks), dim3(BLOCK), 0, (hipStream_t)stream, P);
+    HIPCHK(hipGetLastError());
     return AAC_OK;
 }
 

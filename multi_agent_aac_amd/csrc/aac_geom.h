@@ -484,16 +484,20 @@ __device__ __attribute__((always_inline)) bool ray_poly_entry(double cx, double 
 // ray through a corner) away from the segment's end, mode 1 flags a band case and mode 2 decides: the
 // segment meets the square's boundary iff it meets the closed square and does not lie inside the open
 // one (exact test, a real call).  Ties and exits at t ~ 1 give the distance L either way.
+// (hx, hy): the boundary point the distance was formed from (the radar probe keeps it; c for the
+// along-an-edge case, whose distance is 0).
 template <int EX = 0>
-__device__ __attribute__((always_inline)) bool ray_square(double cx, double cy, double ex, double ey, double x0,
-                                                          double x1, double y0, double y1, double &dout, bool &band,
-                                                          int mode = 1) {
+__device__ __attribute__((always_inline)) bool ray_square_pt(double cx, double cy, double ex, double ey, double x0,
+                                                             double x1, double y0, double y1, double &dout, double &hx,
+                                                             double &hy, bool &band, int mode = 1) {
     double ddx = ex - cx, ddy = ey - cy;
     double tx0, tx1, ty0, ty1;
     // a ray running along an edge from a start point on that edge: the intersection with the
     // boundary is a segment through c, so the distance is 0 (GEOS line.intersection(boundary))
     if ((ddx == 0.0 && (cx == x0 || cx == x1) && cy >= y0 && cy <= y1) ||
         (ddy == 0.0 && (cy == y0 || cy == y1) && cx >= x0 && cx <= x1)) {
+        hx = cx;
+        hy = cy;
         dout = 0.0;
         return true;
     }
@@ -525,15 +529,27 @@ __device__ __attribute__((always_inline)) bool ray_square(double cx, double cy, 
             if (!m) return false;
             double t = tin >= 0.0 ? tin : tout;
             t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t);
-            dout = gdist(cx + t * ddx, cy + t * ddy, cx, cy);
+            hx = cx + t * ddx;
+            hy = cy + t * ddy;
+            dout = gdist(hx, hy, cx, cy);
             return true;
         }
     }
     if (tin > tout || tout < 0.0 || tin > 1.0) return false;
     double t = tin >= 0.0 ? tin : tout;
     if (t > 1.0) return false;
-    dout = gdist(cx + t * ddx, cy + t * ddy, cx, cy);
+    hx = cx + t * ddx;
+    hy = cy + t * ddy;
+    dout = gdist(hx, hy, cx, cy);
     return true;
+}
+
+template <int EX = 0>
+__device__ __attribute__((always_inline)) bool ray_square(double cx, double cy, double ex, double ey, double x0,
+                                                          double x1, double y0, double y1, double &dout, bool &band,
+                                                          int mode = 1) {
+    double hx, hy;
+    return ray_square_pt<EX>(cx, cy, ex, ey, x0, x1, y0, y1, dout, hx, hy, band, mode);
 }
 
 // the float-only forms (UAM radar)
@@ -548,20 +564,37 @@ __device__ inline bool ray_square(double cx, double cy, double ex, double ey, do
     return ray_square<0>(cx, cy, ex, ey, x0, x1, y0, y1, dout, band);
 }
 
-__device__ __attribute__((always_inline)) bool ray_vline(double cx, double cy, double ex, double ey, double lx, double &dout) {
-    if (cx == lx && ex == lx) { dout = 0.0; return true; }
+// the crossings with their point (hx, hy): c when the segment runs along the line (distance 0)
+__device__ __attribute__((always_inline)) bool ray_vline_pt(double cx, double cy, double ex, double ey, double lx,
+                                                            double &dout, double &hx, double &hy) {
+    if (cx == lx && ex == lx) { hx = cx; hy = cy; dout = 0.0; return true; }
     if ((cx - lx) * (ex - lx) > 0.0) return false;
     double t = (lx - cx) / (ex - cx);
-    dout = gdist(lx, cy + t * (ey - cy), cx, cy);
+    hx = lx;
+    hy = cy + t * (ey - cy);
+    dout = gdist(hx, hy, cx, cy);
     return true;
 }
 
-__device__ __attribute__((always_inline)) bool ray_hline(double cx, double cy, double ex, double ey, double ly, double &dout) {
-    if (cy == ly && ey == ly) { dout = 0.0; return true; }
+__device__ __attribute__((always_inline)) bool ray_hline_pt(double cx, double cy, double ex, double ey, double ly,
+                                                            double &dout, double &hx, double &hy) {
+    if (cy == ly && ey == ly) { hx = cx; hy = cy; dout = 0.0; return true; }
     if ((cy - ly) * (ey - ly) > 0.0) return false;
     double t = (ly - cy) / (ey - cy);
-    dout = gdist(cx + t * (ex - cx), ly, cx, cy);
+    hx = cx + t * (ex - cx);
+    hy = ly;
+    dout = gdist(hx, hy, cx, cy);
     return true;
+}
+
+__device__ __attribute__((always_inline)) bool ray_vline(double cx, double cy, double ex, double ey, double lx, double &dout) {
+    double hx, hy;
+    return ray_vline_pt(cx, cy, ex, ey, lx, dout, hx, hy);
+}
+
+__device__ __attribute__((always_inline)) bool ray_hline(double cx, double cy, double ex, double ey, double ly, double &dout) {
+    double hx, hy;
+    return ray_hline_pt(cx, cy, ex, ey, ly, dout, hx, hy);
 }
 
 __device__ __attribute__((always_inline)) void tdcpa(double ox, double oy, double hx, double hy, double ovx, double ovy, double hvx, double hvy,

@@ -350,10 +350,22 @@ class env_simulator:
     step (``display_one_eps_status``, ATT/env:2596-2624).  ``dist_to_goal`` is the progress term as it
     entered the reward: 0.0 on a step that took the crash or goal branch.  Off (the default):
     ``[0.0, None]`` and an untouched holder.
+
+    ``radar_probes=True`` runs a radar probe (``probe.RadarProbe``, include/aac_probe.h) after every step
+    and ``step`` returns the reference's six lists beside the state (ATT/env:1051-1170, :2720), as tuples
+    and numpy, no shapely objects: ``polygons_list`` (the occupied cells, x-major, each a (4, 2) array of
+    the corners (x0, y0), (x1, y0), (x1, y1), (x0, y1)), ``all_agent_st_points`` / ``all_agent_ed_points``
+    (per agent ``{deg: (x, y)}``, the centre / the ray end), ``all_agent_intersection_point_list`` (per
+    agent the hit points of the rays that hit something, in ray order), ``all_agent_line_collection``
+    (per agent the 18 ``((sx, sy), (ex, ey))`` segments) and ``all_agent_mini_intersection_list`` (the
+    hit points again).  The reference's first intersection list also holds the intersections with
+    objects that are not the ray's nearest; those are not kept.  ``last_probes`` holds the full
+    ``RadarProbe.read()`` dict of the step.  Off (the default): six empty lists.
     """
 
     def __init__(self, world_map, building_polygons=None, grid_length=10, bound=None, allGridPoly=None,
-                 agentConfig=None, radar_mode="drones", compat=True, seed=None, reward_terms=False):
+                 agentConfig=None, radar_mode="drones", compat=True, seed=None, reward_terms=False,
+                 radar_probes=False):
         occ = np.asarray(world_map, dtype=np.uint8)
         self.world_map_2D = occ
         self.buildingPolygons = building_polygons
@@ -369,6 +381,9 @@ class env_simulator:
         self._rng = np.random.default_rng(seed)
         self._env = None
         self.reward_terms = bool(reward_terms)
+        self.radar_probes = bool(radar_probes)
+        self.last_probes = None
+        self._probe = None
 
     def create_world(self, total_agentNum, n_actions, gamma, tau, target_update, largest_Nsigma, smallest_Nsigma,
                      ini_Nsigma, max_xy, max_spd, acc_range, full_observable_critic_flag=True):
@@ -388,6 +403,14 @@ class env_simulator:
         self._env_agentwise = None
         if self.reward_terms:
             self._env.use_terms_buffer()
+        if self.radar_probes:
+            from .probe import RadarProbe
+            self._probe = RadarProbe.for_env(self._env)
+            g = float(self.gridlength)
+            ox, oy = math.ceil(self.bound[0] / g) * g, math.ceil(self.bound[2] / g) * g
+            self._cell_polys = [np.array([(x - g / 2, y - g / 2), (x + g / 2, y - g / 2), (x + g / 2, y + g / 2),
+                                          (x - g / 2, y + g / 2)])
+                                for i, j in zip(*np.nonzero(self.world_map_2D)) for x, y in ((ox + g * i, oy + g * j),)]
 
     # ---------------------------------------------------------------- OD (ATT/env:251-347)
     def _draw_od(self, N):
@@ -496,7 +519,23 @@ class env_simulator:
             self._last["terms"] = self._env.terms[0].cpu().numpy()
         self._sync_agents()
         state, norm = self._states()
-        return state, norm, [], [], [], [], [], []
+        if self._probe is None:
+            return state, norm, [], [], [], [], [], []
+        return (state, norm) + self._probe_lists()
+
+    def _probe_lists(self):
+        """The reference's six lists of the step (class docstring) from a probe of the live state."""
+        self._probe.run()
+        pr = self.last_probes = self._probe.read()
+        st, ed, hits, lines = [], [], [], []
+        for i, ag in self.all_agents.items():
+            c = (float(ag.pos[0]), float(ag.pos[1]))
+            ends = [(float(x), float(y)) for x, y in pr["end"][0, i]]
+            st.append({20 * r: c for r in range(N_RAYS)})
+            ed.append({20 * r: ends[r] for r in range(N_RAYS)})
+            hits.append([(float(x), float(y)) for x, y in pr["point"][0, i][pr["kind"][0, i] != 0]])
+            lines.append([(c, ends[r]) for r in range(N_RAYS)])
+        return list(self._cell_polys), st, ed, hits, lines, [list(h) for h in hits]
 
     def ss_reward(self, current_ts, step_reward_record, eps_status_holder, step_collision_record, xy=(None, None),
                   full_observable_critic_flag=True, args=None):
