@@ -26,6 +26,7 @@ EXPORTS = (
     "aac_terms_record",
     "aac_clip_last_error", "aac_clip_partials", "aac_clip_sumsq", "aac_adam_flat_clip",
     "aac_env_probe",
+    "aac_env_reward_map",
 )
 
 vp = ctypes.c_void_p
@@ -126,6 +127,10 @@ class ProbeOut(ctypes.Structure):          # aac_probe_out (include/aac_probe.h)
     _fields_ = [(n, vp) for n in ("dist", "point", "end", "kind", "id")]
 
 
+class RmapOut(ctypes.Structure):           # aac_rmap_out (include/aac_rmap.h)
+    _fields_ = [(n, vp) for n in ("reward", "terms", "mask", "done", "bbc")]
+
+
 _lib = None
 
 
@@ -186,6 +191,8 @@ def lib():
         L.aac_adam_flat_clip.argtypes = [ctypes.POINTER(ClipJob), i32, i32, vp]
     if hasattr(L, "aac_env_probe") or not os.environ.get("AAC_LIB"):
         L.aac_env_probe.argtypes = [vp, vp, vp, ctypes.c_int64, vp, ctypes.POINTER(ProbeOut), vp]
+    if hasattr(L, "aac_env_reward_map") or not os.environ.get("AAC_LIB"):
+        L.aac_env_reward_map.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_int64, ctypes.POINTER(RmapOut), vp]
     for name in EXPORTS:
         if os.environ.get("AAC_LIB") and not hasattr(L, name):
             continue          # an A/B experiment build of an earlier revision

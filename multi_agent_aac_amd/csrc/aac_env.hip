@@ -28,6 +28,7 @@
 
 #include "../../include/aac_env.h"
 #include "../../include/aac_probe.h"
+#include "../../include/aac_rmap.h"
 #include "../../include/aac_terms.h"
 #include "aac_geom.h"
 #include "aac_wave.h"
@@ -1722,6 +1723,252 @@ __global__ void __launch_bounds__(BLOCK) radar_probe_kernel(ProbeArgs P) {
     }
 }
 
+// --------------------------------------------------------------------------------- reward map
+// include/aac_rmap.h: row m = what ss_reward would hand agent agent[m] of env env_idx[m] standing at
+// points[m] with pre_pos pre[m], everything else the handle's live state.  One lane per row; the lane
+// reads the subject's state and its env's other agents from global memory (L2: the rows of a sweep share
+// them) and writes nothing but the row's outputs.  The predicates and the arithmetic are the step
+// kernel's (phase 3-4 for ATT, wgru_reward for WGRU), restated without their state writes: no waypoint
+// pop, no reach / wall update, no goal rewrite, no band or fix-up list entry.
+struct RmapArgs {
+    int64_t M;
+    const double *points, *pre;            // [M][2]; pre null: pre_pos = the point
+    const int32_t *env_idx, *agent;        // [M] or null (0)
+    const double *rmin;                    // [M] or null: the exact obstacle radar at the point (variant 1)
+    double *reward, *terms;                // terms may be null
+    uint8_t *mask, *done, *bbc;
+};
+static_assert(sizeof(aac_rmap_out) == AAC_RMAP_OUT_BYTES, "the header's constant for bindings");
+#define RMAP_BLOCK 64     // one wave per workgroup: a 2 500-row sweep spreads over 40 CUs
+
+// wgru_reward without its writes: the waypoint search works on a private copy of the removed-waypoint
+// bits, the waypoints come from global memory.  t: the row's 12 terms (include/aac_terms.h)
+__device__ __attribute__((noinline)) double wgru_reward_ro(const Args &A, const double2 *wp, double2 pp, double2 p, double2 v,
+                                                          uint32_t rm, int cnt, double rmin, int goal, int bnd,
+                                                          int building, int &flag, int &done, int &cg, uint8_t &fl,
+                                                          double2 start, double *t) {
+    const double px = p.x, py = p.y, pb = A.pb;
+    int nrem = cnt - __popc(rm & (cnt >= 32 ? 0xffffffffu : ((1u << cnt) - 1u)));
+    double smallest = INFINITY;
+    double2 nx = make_double2(0.0, 0.0);
+    for (int k = 0; k < cnt; ++k) {
+        if ((rm >> k) & 1u) continue;
+        const double2 w = wp[k];
+        const double d = gdist(px, py, w.x, w.y);
+        if (d < smallest) {
+            smallest = d;
+            nx = w;
+            if (smallest < 5) {
+                flag = 1;
+                if (nrem > 1) {
+                    rm |= 1u << k;
+                    --nrem;
+                    double best = INFINITY;
+                    for (int q = 0; q < cnt; ++q) {
+                        if ((rm >> q) & 1u) continue;
+                        const double2 uq = wp[q];
+                        const double dd = gdist(uq.x, uq.y, px, py);
+                        if (dd < best) {
+                            best = dd;
+                            nx = uq;
+                        }
+                    }
+                }
+                break;
+            }
+        }
+    }
+    const double dafter = npnorm(px - nx.x, py - nx.y);
+    const double dtg = 1 * (npnorm(pp.x - nx.x, pp.y - nx.y) - dafter);
+    // cross_track_error (WGRU/env:2621-2632), with wgru_reward's bounding-box skip
+    double cross;
+    {
+        double best = INFINITY;
+        double2 a = start, q = a;
+        for (int k = 0; k < cnt; ++k) {
+            const double2 b = wp[k];
+            {
+                const double ox = fmax(fmax(fmin(a.x, b.x) - px, px - fmax(a.x, b.x)), 0.0);
+                const double oy = fmax(fmax(fmin(a.y, b.y) - py, py - fmax(a.y, b.y)), 0.0);
+                if (ox * ox + oy * oy > best * best * (1.0 + 1e-8)) {
+                    a = b;
+                    continue;
+                }
+            }
+            const double d = point_to_segment(px, py, a.x, a.y, b.x, b.y);
+            if (d < best) {
+                best = d;
+                q = segment_closest_point(px, py, a.x, a.y, b.x, b.y);
+            }
+            if (best <= 0.0) break;
+            a = b;
+        }
+        cross = gdist(px, py, q.x, q.y);
+    }
+    double dref;
+    if (cross <= pb) dref = 3 * (((0 - 1) / (pb - 0)) * cross + 1);
+    else dref = -3 * 1;
+    const double thr = 2 * pb;
+    const double sp = npnorm(v.x, v.y);
+    const double clip = sp < 0 ? 0 : (sp > thr ? thr : sp);
+    const double ssp = 3 * ((thr - clip) * (1.0 / thr));
+    const double nbp = wgru_nbp(rmin, pb);
+    for (int k = 0; k < AAC_TERMS_W; ++k) t[k] = 0.0;
+    t[8] = cross;
+    t[9] = sp;
+    t[10] = dafter;
+    t[11] = rmin;
+    double r;
+    if (bnd || building) {
+        done = 1;
+        fl |= bnd ? 8 : 16;
+        r = (((((0.0 + dref) - 5) + dtg) - ssp) + 0.0) - nbp;
+        t[0] = -5.0;
+        t[2] = dref;
+        t[3] = dtg;
+        t[4] = -ssp;
+        t[5] = -nbp;
+    } else if (goal) {
+        cg = 1;
+        r = (0.0 + 5) + 0.0;
+        t[0] = 5.0;
+    } else {
+        r = 0.0;
+        if (flag && nrem > 1) r = r + 3;
+        t[1] = r;
+        t[2] = dref;
+        t[3] = dtg;
+        t[4] = -ssp;
+        t[5] = -nbp;
+        r = ((((r + dref) + dtg) - ssp) + 0.0 - nbp) + 0.0;
+    }
+    return r;
+}
+
+template <int VAR>
+__global__ void __launch_bounds__(RMAP_BLOCK) reward_map_kernel(Args A, RmapArgs Q) {
+    const int64_t m = (int64_t)blockIdx.x * RMAP_BLOCK + threadIdx.x;
+    if (m >= Q.M) return;
+    const int N = A.N;
+    int e = Q.env_idx ? Q.env_idx[m] : 0, i = Q.agent ? Q.agent[m] : 0;
+    e = e < 0 ? 0 : (e > A.E - 1 ? A.E - 1 : e);
+    i = i < 0 ? 0 : (i > N - 1 ? N - 1 : i);
+    const size_t ai = (size_t)e * N + i;
+    const double px = Q.points[2 * m], py = Q.points[2 * m + 1], pb = A.pb;
+    const double2 pp = Q.pre ? make_double2(Q.pre[2 * m], Q.pre[2 * m + 1]) : make_double2(px, py);
+    const double2 v = A.vel[ai], g = A.goal[ai];
+    int mi = A.map_idx[e];
+    mi = mi < 0 ? 0 : (mi > A.n_maps - 1 ? A.n_maps - 1 : mi);
+    const uint8_t *occ = A.occ + (size_t)mi * A.gw * A.gh;
+    int wcnt = A.wp_cnt[ai];
+    wcnt = wcnt < 0 ? 0 : (wcnt > A.W ? A.W : wcnt);
+    const int cur = A.wp_cur[ai];
+    const double2 *pos = A.pos + (size_t)e * N;
+
+    // ---- ss_reward's predicates, as step_kernel's agent phase forms them
+    int ncoll = 0, last_coll = -1, nearest = -1;
+    double shortest = INFINITY;
+    for (int j = 0; j < N; ++j) {
+        if (j == i) continue;
+        const double2 q = pos[j];
+        double d = npnorm(px - q.x, py - q.y);
+        if (d < shortest) {
+            shortest = d;
+            nearest = j;
+        }
+        if (d <= pb * 2) {
+            ++ncoll;
+            last_coll = j;
+        }
+    }
+    const double c_drone = 1 + (2.5 / (10 - 2.5)), m_drone = (0 - 1) / (10 - 2.5);
+    double pen = 0;
+    for (int j = 0; j < N && !VAR; ++j) {
+        if (j == i) continue;
+        const double2 q = pos[j];
+        double d = npnorm(px - q.x, py - q.y);
+        if (d >= 2.5 && d <= 10) pen = pen + (1 * (m_drone * shortest + c_drone));
+        else pen = pen + 0;
+    }
+    int building = 0;
+    {
+        int ci = (int)floor((px - A.gx0) / 10.0 + 0.5), cj = (int)floor((py - A.gy0) / 10.0 + 0.5);
+        for (int ii = ci - 1; ii <= ci + 1 && !building; ++ii)
+            for (int jj = cj - 1; jj <= cj + 1; ++jj) {
+                if (ii < 0 || jj < 0 || ii >= A.gw || jj >= A.gh) continue;
+                if (!occ[ii * A.gh + jj]) continue;
+                if (building_hit<EXACT_COLD(VAR)>(px, py, A.gx0 + 10.0 * ii, A.gy0 + 10.0 * jj, pb)) {
+                    building = 1;
+                    break;
+                }
+            }
+    }
+    const int goal = goal_reached<EXACT_COLD(VAR)>(px, py, g.x, g.y, pb);
+    const int bnd = bound_crash(A, pp.x, pp.y, px, py);
+    int done = 0, cg = 0, wpf = 0;
+    uint8_t fl = 0;
+    double r;
+    double t[AAC_TERMS_W];
+    if (VAR) {
+        double rmin;
+        if (Q.rmin) {
+            rmin = Q.rmin[m];
+        } else {      // the exact obstacle radar at the point, as band_fix_kernel recomputes a listed reward's
+            const double2 p2 = make_double2(px, py);
+            rmin = INFINITY;
+            for (int ray = 0; ray < NRAY; ++ray) {
+                const double d = radar_ray_exact(&p2, 1, 0, ray, pb, A.radar_len, AAC_RADAR_OBSTACLES, occ, A.gw, A.gh,
+                                                 A.gx0, A.gy0, A.bound);
+                rmin = d < rmin ? d : rmin;
+            }
+        }
+        r = wgru_reward_ro(A, A.wp + ai * A.W, pp, make_double2(px, py), v, (uint32_t)cur, wcnt, rmin, goal, bnd, building,
+                           wpf, done, cg, fl, A.start[ai], t);
+    } else {
+        const double2 w0 = A.wp0[ai];
+        wpf = gdist(px, py, w0.x, w0.y) < 5;
+        const double before = npnorm(pp.x - g.x, pp.y - g.y);
+        const double after = npnorm(px - g.x, py - g.y);
+        const double dtg = (1 * (before - after)) / A.vmax;
+        if (bnd) {
+            r = ((0.0 - 20) - 0.0) - 0;
+            done = 1;
+            fl |= 8;
+        } else if (ncoll > 0) {
+            r = ((0.0 - 20) - 0.0) - pen;
+            done = 1;
+            fl |= 16;
+            if (last_coll == nearest) fl |= 32;
+        } else if (goal) {
+            r = (0.0 + 20) + 0.0;
+            cg = 1;
+        } else {
+            r = dtg - pen;
+        }
+        const bool crash = bnd || ncoll > 0, normal = !crash && !goal;
+        for (int k = 0; k < AAC_TERMS_W; ++k) t[k] = 0.0;
+        t[0] = crash ? -20.0 : (goal ? 20.0 : 0.0);
+        t[3] = normal ? dtg : 0.0;
+        t[6] = (!bnd && ncoll > 0) || normal ? -pen : 0.0;
+        t[9] = npnorm(v.x, v.y);
+        t[10] = after;
+    }
+    uint8_t mk = (uint8_t)(bnd | ((ncoll > 0) << 1) | (goal << 2) | (building << 3) | (wpf << 4));
+    if (cg) mk |= 32;
+    Q.reward[m] = r;
+    Q.mask[m] = mk;
+    Q.done[m] = (uint8_t)done;
+    // bound_building_check as this agent alone sets it: ATT [bound, 0, drone, last contact == nearest],
+    // variant 1 [bound, building, 0, 0]
+    const uint8_t b0 = (fl >> 3) & 1, b2 = (fl >> 4) & 1, b3 = (fl >> 5) & 1;
+    Q.bbc[4 * m + 0] = b0;
+    Q.bbc[4 * m + 1] = VAR ? b2 : 0;
+    Q.bbc[4 * m + 2] = VAR ? 0 : b2;
+    Q.bbc[4 * m + 3] = VAR ? 0 : b3;
+    if (Q.terms)
+        for (int k = 0; k < AAC_TERMS_W; ++k) Q.terms[(size_t)m * AAC_TERMS_W + k] = t[k];
+}
+
 // ------------------------------------------------------------------------------ host side
 thread_local std::string g_err;
 // Auto-reset over the packed list of done envs: -1 (default) per variant -- off for the ATT env, where
@@ -2313,6 +2560,36 @@ int aac_env_probe(aac_env *h, const double *pos_dev, const int32_t *map_idx_dev,
     P.kind = out->kind;
     P.id = out->id;
     hipLaunchKernelGGL(radar_probe_kernel, dim3((unsigned)blocks), dim3(BLOCK), 0, (hipStream_t)stream, P);
+    HIPCHK(hipGetLastError());
+    return AAC_OK;
+}
+
+int aac_env_reward_map(aac_env *h, const double *points, const double *pre, const int32_t *env_idx, const int32_t *agent,
+                       const double *rmin, int64_t M, const aac_rmap_out *out, void *stream) {
+    if (!h || !out || !points) return fail(AAC_E_INVALID, "reward_map: null handle, points or out");
+    if (!out->reward || !out->mask || !out->done || !out->bbc)
+        return fail(AAC_E_INVALID, "reward_map: reward, mask, done, bbc required");
+    if ((reinterpret_cast<uintptr_t>(points) | reinterpret_cast<uintptr_t>(pre) | reinterpret_cast<uintptr_t>(rmin) |
+         reinterpret_cast<uintptr_t>(out->reward) | reinterpret_cast<uintptr_t>(out->terms)) & 7)
+        return fail(AAC_E_INVALID, "reward_map: points, pre, rmin, reward and terms must be 8-byte aligned");
+    const int64_t blocks = (M + RMAP_BLOCK - 1) / RMAP_BLOCK;
+    if (M < 1 || blocks > 0x7fffffff) return fail(AAC_E_INVALID, "reward_map: M out of range");
+    const aac_step_out none{};
+    const Args A = make_args(h, &none);
+    RmapArgs Q;
+    Q.M = M;
+    Q.points = points;
+    Q.pre = pre;
+    Q.env_idx = env_idx;
+    Q.agent = agent;
+    Q.rmin = rmin;
+    Q.reward = out->reward;
+    Q.terms = out->terms;
+    Q.mask = out->mask;
+    Q.done = out->done;
+    Q.bbc = out->bbc;
+    if (A.variant) hipLaunchKernelGGL(reward_map_kernel<1>, dim3((unsigned)blocks), dim3(RMAP_BLOCK), 0, (hipStream_t)stream, A, Q);
+    else hipLaunchKernelGGL(reward_map_kernel<0>, dim3((unsigned)blocks), dim3(RMAP_BLOCK), 0, (hipStream_t)stream, A, Q);
     HIPCHK(hipGetLastError());
     return AAC_OK;
 }

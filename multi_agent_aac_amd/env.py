@@ -539,7 +539,15 @@ class env_simulator:
 
     def ss_reward(self, current_ts, step_reward_record, eps_status_holder, step_collision_record, xy=(None, None),
                   full_observable_critic_flag=True, args=None):
-        """ATT/env:2105 -- returns the kernel's reward/done/check_goal/bbc of the last step."""
+        """ATT/env:2105 -- returns the kernel's reward/done/check_goal/bbc of the last step.
+
+        ``xy=(x, y)``: the reference's map mode (ATT/env:2133-2138) -- agent 0 alone evaluated at (x, y)
+        with ``pre_pos = pos = xy``, as a one-row reward map (``rewardmap.RewardMap``): ``reward`` and
+        ``done`` of length 1, ``check_goal`` of length N with entry 0 set, ``step_reward_record[0]``
+        updated.  Unlike the reference's, the call leaves ``all_agents[0].pos`` and the device state as
+        they were."""
+        if xy is not None and xy[0] is not None and xy[1] is not None:
+            return self._ss_reward_at(xy, step_reward_record, eps_status_holder, step_collision_record)
         last = self._last
         mask = last["mask"]
         N = self._env.N
@@ -568,3 +576,19 @@ class env_simulator:
                 step_reward_record[i] = [0.0, None]
         bbc = [bool(v) for v in last["bbc"]]
         return reward, done, check_goal, step_reward_record, eps_status_holder, step_collision_record, bbc
+
+    def _ss_reward_at(self, xy, step_reward_record, eps_status_holder, step_collision_record):
+        """``ss_reward`` in map mode: one reward-map row of agent 0 at ``xy`` (``pre = point``; the radar
+        minimum, which only the WGRU reward reads, from the held radar row as in the reference)."""
+        if getattr(self, "_rmap", None) is None:
+            from .rewardmap import RewardMap
+            self._rmap = RewardMap.for_env(self._env)
+        rmin = self._rmap.held_rmin() if self._env.variant else None
+        self._rmap.at(np.array([[float(xy[0]), float(xy[1])]]), rmin=rmin)
+        row = self.last_map_row = {k: v[0] for k, v in self._rmap.read().items()}
+        check_goal = [False] * self._env.N
+        check_goal[0] = bool(row["mask"] & 32)
+        if step_reward_record is not None:
+            step_reward_record[0] = [0.0, float(row["terms"][3])]
+        return ([np.float64(row["reward"])], [bool(row["done"])], check_goal, step_reward_record, eps_status_holder,
+                step_collision_record, [bool(v) for v in row["bbc"]])
