@@ -27,6 +27,7 @@ EXPORTS = (
     "aac_clip_last_error", "aac_clip_partials", "aac_clip_sumsq", "aac_adam_flat_clip",
     "aac_env_probe",
     "aac_env_reward_map",
+    "aac_uam_reward_map",
 )
 
 vp = ctypes.c_void_p
@@ -131,6 +132,10 @@ class RmapOut(ctypes.Structure):           # aac_rmap_out (include/aac_rmap.h)
     _fields_ = [(n, vp) for n in ("reward", "terms", "mask", "done", "bbc")]
 
 
+class UamRmapOut(ctypes.Structure):        # aac_uam_rmap_out (include/aac_uam_rmap.h)
+    _fields_ = [(n, vp) for n in ("reward", "terms", "mask", "done", "bbc", "flags", "rays")]
+
+
 _lib = None
 
 
@@ -193,6 +198,8 @@ def lib():
         L.aac_env_probe.argtypes = [vp, vp, vp, ctypes.c_int64, vp, ctypes.POINTER(ProbeOut), vp]
     if hasattr(L, "aac_env_reward_map") or not os.environ.get("AAC_LIB"):
         L.aac_env_reward_map.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_int64, ctypes.POINTER(RmapOut), vp]
+    if hasattr(L, "aac_uam_reward_map") or not os.environ.get("AAC_LIB"):
+        L.aac_uam_reward_map.argtypes = [vp, vp, vp, vp, vp, vp, vp, ctypes.c_int64, ctypes.POINTER(UamRmapOut), vp]
     for name in EXPORTS:
         if os.environ.get("AAC_LIB") and not hasattr(L, name):
             continue          # an A/B experiment build of an earlier revision

@@ -25,6 +25,7 @@
 
 #include "../../include/aac_uam.h"
 #include "../../include/aac_terms.h"
+#include "../../include/aac_uam_rmap.h"
 #include "aac_geom.h"
 #include "aac_wave.h"
 
@@ -1034,6 +1035,201 @@ __global__ void __launch_bounds__(1024) uam_compact_kernel(const uint8_t *__rest
     aacw::compact_flags(mask, E, rlist);
 }
 
+// ------------------------------------------------------------------------------ reward map
+// ss_reward_Mar_changeskin at any test position (include/aac_uam_rmap.h; UAM/main:434-505, UAM/env:3939-3944):
+// row m is what phases 5-6 of uam_step_kernel would hand aircraft agent[m] of env env_idx[m] if it stood at
+// points[m] with pre_pos = pre[m], everything else the handle's live state.  Read-only.
+// Work mapping: a 256-thread workgroup takes RMAP_ROWS = 14 rows; thread t < 14 * 18 is the work item
+// (row t / 18, ray t % 18) of the radar and walks that ray's clips itself (the others' positions from global
+// memory: one env per sweep in the common case, L2-resident); the rays meet in LDS, and after the barrier
+// the ray-0 lane of each row (spread over the four waves) takes their minimum and forms the reward.  No
+// cross-lane operation; the one barrier is reached by every thread.
+#define RMAP_ROWS AAC_UAM_RMAP_ROWS
+
+struct UMap {
+    int64_t M;
+    const double *points, *pre, *rmin;
+    const int32_t *env_idx, *agent;
+    const uint8_t *prev2;
+    double *reward, *terms, *rays;
+    uint8_t *mask, *done, *bbc, *flags;
+};
+
+// ray_clip_dist on positions instead of the step's Lds: segment c->e against the 64-gon(q, rad), the
+// candidate test first (the step's pair pass is only a superset of it)
+__device__ inline double ray_clip_dist_at(double cx, double cy, double ex, double ey, double inv_l2, double qx,
+                                          double qy, double rad, bool &hit) {
+    double t;
+    hit = ray_gon_candidate(cx, cy, ex, ey, qx, qy, rad, inv_l2) &&
+          ray_gon_boundary_cand(cx, cy, ex, ey, qx, qy, rad, t);
+    return hit ? gdist(cx + t * (ex - cx), cy + t * (ey - cy), cx, cy) : 0.0;
+}
+
+__global__ void __launch_bounds__(BLOCK) uam_reward_map_kernel(UArgs A, UMap Q) {
+    __shared__ double s_rad[RMAP_ROWS][NRAY];
+    const int N = A.N;
+    const int t = threadIdx.x;
+    const int lr = t / NRAY, r = t - lr * NRAY;
+    const int64_t m = (int64_t)blockIdx.x * RMAP_ROWS + lr;
+    const bool on = lr < RMAP_ROWS && m < Q.M;
+    int e = 0, i = 0;
+    double px = 0.0, py = 0.0;
+    if (on) {
+        if (Q.env_idx) e = Q.env_idx[m];
+        if (Q.agent) i = Q.agent[m];
+        e = e < 0 ? 0 : (e >= A.E ? A.E - 1 : e);
+        i = i < 0 ? 0 : (i >= N ? N - 1 : i);
+        px = Q.points[2 * m];
+        py = Q.points[2 * m + 1];
+    }
+    const size_t eb = (size_t)e * N, ai = eb + i;
+
+    // ---- radar at the point (radar_phase 3a-3b for one ray, the clips in this lane)
+    if (on && !Q.rmin) {
+        const double cx = px, cy = py;
+        const double ex = cx + A.radar_len * c_tab.ray_c[r], ey = cy + A.radar_len * c_tab.ray_s[r];
+        double best = gdist(ex, ey, cx, cy);
+        double d;
+        const double *rw = c_world.runway;
+        if (fmax(cx, ex) >= rw[0] - 1e-9 && fmin(cx, ex) <= rw[1] + 1e-9 && fmax(cy, ey) >= rw[2] - 1e-9 &&
+            fmin(cy, ey) <= rw[3] + 1e-9 && ray_square(cx, cy, ex, ey, rw[0], rw[1], rw[2], rw[3], d) && d < best)
+            best = d;
+        const double *b = A.bound;
+        if (ray_vseg(cx, cy, ex, ey, b[0], b[2], b[3], d) && d < best) best = d;
+        if (ray_vseg(cx, cy, ex, ey, b[1], b[2], b[3], d) && d < best) best = d;
+        if (ray_hseg(cx, cy, ex, ey, b[3], b[0], b[1], d) && d < best) best = d;
+        if (ray_hseg(cx, cy, ex, ey, b[2], b[0], b[1], d) && d < best) best = d;
+        const double inv_l2 = 1.0 / ((ex - cx) * (ex - cx) + (ey - cy) * (ey - cy));
+        bool hit;
+        for (int k = 0; k < 2; ++k) {
+            const double2 c = A.clouds[(size_t)e * 2 + k];
+            d = ray_clip_dist_at(cx, cy, ex, ey, inv_l2, c.x, c.y, c_world.radius[k], hit);
+            if (hit && d < best) best = d;
+        }
+        for (int j = 0; j < N; ++j) {
+            if (j == i) continue;
+            const double2 q = A.pos[eb + j];
+            d = ray_clip_dist_at(cx, cy, ex, ey, inv_l2, q.x, q.y, A.pb, hit);
+            if (hit && d < best) best = d;
+        }
+        s_rad[lr][r] = best;
+        if (Q.rays) Q.rays[m * NRAY + r] = best;
+    }
+    __syncthreads();
+    if (!on || r != 0) return;
+
+    // ---- phase 5 of the step for this aircraft alone
+    const double pb = A.pb;
+    double ppx = px, ppy = py;
+    if (Q.pre) {
+        ppx = Q.pre[2 * m];
+        ppy = Q.pre[2 * m + 1];
+    }
+    const double2 g = A.goal[ai];
+    const int goal = gons_meet_band<true>(px, py, g.x, g.y, pb, 1.0, false);
+    const int me = A.reach[ai] || goal;
+    const uint8_t old0 = Q.prev2 ? Q.prev2[2 * m] : A.top2[ai * 2 + 0];
+    const uint8_t old1 = Q.prev2 ? Q.prev2[2 * m + 1] : A.top2[ai * 2 + 1];
+    // order_phase is a stable sort by (distance, index): the nearest is the minimum of (d, j), the last
+    // collider of the sorted walk the maximum of (d, j) among the colliders
+    int ncoll = 0, nearest = -1, last = -1, prev_two = 0;
+    double shortest = INFINITY, lastd = -INFINITY;
+    for (int j = 0; j < N; ++j) {
+        if (j == i) continue;
+        const double2 q = A.pos[eb + j];
+        const double d = npnorm(q.x - px, q.y - py);
+        if (d < shortest) {
+            shortest = d;
+            nearest = j;
+        }
+        if (d <= pb * 2 && !(A.reach[eb + j] || me)) {
+            ++ncoll;
+            if (d >= lastd) {
+                lastd = d;
+                last = j;
+            }
+            prev_two |= (j == old0) || (j == old1);
+        }
+    }
+    int cloud = 0;
+    if (!me) {
+        const double *rw = c_world.runway;
+        cloud = gon_rect_overlap(px, py, pb, rw);
+        for (int k = 0; k < 2 && !cloud; ++k) {
+            const double2 c = A.clouds[(size_t)e * 2 + k];
+            cloud = gons_meet_band<true>(px, py, c.x, c.y, pb, c_world.radius[k], true);
+        }
+    }
+    const double2 s = A.start[ai];
+    const double L = gdist(g.x, g.y, s.x, s.y);
+    const double rdx = g.x - s.x, rdy = g.y - s.y;
+    double fr = ((px - s.x) * rdx + (py - s.y) * rdy) / (rdx * rdx + rdy * rdy);
+    fr = fr < 0.0 ? 0.0 : (fr > 1.0 ? 1.0 : fr);
+    const double cross = gdist(px, py, s.x + fr * rdx, s.y + fr * rdy);
+    const double left = cross + (L - fr * L);
+    const double dtg = 5.0 * (1 - (left / L));
+    uint8_t fl = 0;
+    double ndv = 0.0;
+    if (nearest >= 0 && shortest >= 2.0 && shortest <= 5.0) {
+        const double2 q = A.pos[eb + nearest];
+        const double br = bearing(px, py, q.x, q.y);
+        fl |= 1 | ((br >= 90.0 && br <= 180) << 1);
+        ndv = ((0 - 1) / (5.0 - 2.0)) * shortest + (1 + (2.0 / (5.0 - 2.0)));
+    }
+    double mn;
+    if (Q.rmin) {
+        mn = Q.rmin[m];
+    } else {
+        mn = s_rad[lr][0];
+        for (int k = 1; k < NRAY; ++k) mn = s_rad[lr][k] < mn ? s_rad[lr][k] : mn;
+    }
+    const double nbp = (mn >= pb && mn <= 5.0) ? 2.0 * (((0 - 1) / (5.0 - pb)) * mn + 2) : 0.0;
+    const int bnd = capsule_crash(pb, A.bound, ppx, ppy, px, py);
+    int kind;
+    if (bnd) kind = 0;
+    else if (cloud) kind = 1;
+    else if (ncoll > 0) {
+        kind = 2;
+        const double2 q = A.pos[eb + last];
+        const double br = bearing(px, py, q.x, q.y);
+        fl |= ((br >= 90.0 && br <= 180) << 2) | (prev_two << 3);
+    } else if (goal) kind = 3;
+    else kind = 4;
+    // ---- phase 6 with the coefficients of this aircraft alone
+    const double ndc = ((fl & 1) && (fl & 2)) ? 2.0 * 2 : 2.0;
+    const double crash = (kind == 2 && (fl & 4)) ? 50.0 * 2 : 50.0;
+    const double nd = (fl & 1) ? ndc * ndv : ndc * 0;
+    double rew;
+    if (kind < 3) rew = 0 - crash;
+    else if (kind == 3) rew = 0 + 50.0 + 0;
+    else rew = ((0 + dtg) - nbp) - nd;
+    Q.reward[m] = rew;
+    Q.done[m] = (uint8_t)(kind < 3);
+    Q.mask[m] = (uint8_t)(bnd | (cloud << 1) | ((ncoll > 0) << 2) | (goal << 3) | ((kind == 3) << 4) |
+                          ((kind == 2 && prev_two) << 5));
+    Q.flags[m] = fl;
+    Q.bbc[4 * m + 0] = kind == 0;
+    Q.bbc[4 * m + 1] = kind == 1;
+    Q.bbc[4 * m + 2] = kind == 2;
+    Q.bbc[4 * m + 3] = kind == 2 && (fl & 8);
+    if (Q.terms) {
+        const double2 v = A.vel[ai];
+        double *q = Q.terms + m * AAC_TERMS_W;
+        q[0] = kind < 3 ? -crash : (kind == 3 ? 50.0 : 0.0);
+        q[1] = 0.0;
+        q[2] = 0.0;
+        q[3] = kind == 4 ? dtg : 0.0;
+        q[4] = 0.0;
+        q[5] = kind == 4 ? -nbp : 0.0;
+        q[6] = kind == 4 ? -nd : 0.0;
+        q[7] = 0.0;
+        q[8] = cross;
+        q[9] = npnorm(v.x, v.y);
+        q[10] = npnorm(px - g.x, py - g.y);
+        q[11] = mn;
+    }
+}
+
 // exactness check of ray_gon_boundary's fast paths against the full clip (aac_uam_ray_gon_check):
 // random segments of radar length from points around a 64-gon, focused on the inside / annulus /
 // near-tangent cases; counts results that differ in the hit flag or any bit of t
@@ -1400,6 +1596,39 @@ int aac_uam_auto_reset(aac_uam *h, const uint8_t *env_done, const aac_uam_out *o
         R.list = h->rlist;
     }
     return launch_reset(h, R, o, stream);
+}
+
+int aac_uam_reward_map(aac_uam *h, const double *points, const double *pre, const int32_t *env_idx, const int32_t *agent,
+                       const double *rmin, const uint8_t *prev2, int64_t M, const aac_uam_rmap_out *out, void *stream) {
+    if (!h || !out || !points) return ufail(AAC_E_INVALID, "uam_reward_map: null handle, points or out");
+    if (!out->reward || !out->mask || !out->done || !out->bbc || !out->flags)
+        return ufail(AAC_E_INVALID, "uam_reward_map: reward, mask, done, bbc, flags required");
+    if ((reinterpret_cast<uintptr_t>(points) | reinterpret_cast<uintptr_t>(pre) | reinterpret_cast<uintptr_t>(rmin) |
+         reinterpret_cast<uintptr_t>(out->reward) | reinterpret_cast<uintptr_t>(out->terms) |
+         reinterpret_cast<uintptr_t>(out->rays)) & 7)
+        return ufail(AAC_E_INVALID, "uam_reward_map: points, pre, rmin, reward, terms and rays must be 8-byte aligned");
+    const int64_t blocks = (M + RMAP_ROWS - 1) / RMAP_ROWS;
+    if (M < 1 || blocks > 0x7fffffff) return ufail(AAC_E_INVALID, "uam_reward_map: M out of range");
+    const aac_uam_out none{};
+    const UArgs A = make_uargs(h, &none);
+    UMap Q;
+    Q.M = M;
+    Q.points = points;
+    Q.pre = pre;
+    Q.rmin = rmin;
+    Q.env_idx = env_idx;
+    Q.agent = agent;
+    Q.prev2 = prev2;
+    Q.reward = out->reward;
+    Q.terms = out->terms;
+    Q.rays = out->rays;
+    Q.mask = out->mask;
+    Q.done = out->done;
+    Q.bbc = out->bbc;
+    Q.flags = out->flags;
+    hipLaunchKernelGGL(uam_reward_map_kernel, dim3((unsigned)blocks), dim3(BLOCK), 0, (hipStream_t)stream, A, Q);
+    UCHK(hipGetLastError());
+    return AAC_OK;
 }
 
 int aac_uam_bank_build(int32_t n, int32_t N, uint64_t seed, double *start, double *goal, int32_t *clouds) {

@@ -27,7 +27,7 @@ BOUND = (0.0, 40.0, 0.0, 40.0)               # UAM/params:32-36
 EXPORTS = ("aac_uam_create", "aac_uam_destroy", "aac_uam_last_error", "aac_uam_reset", "aac_uam_step",
            "aac_uam_set_bank", "aac_uam_auto_reset", "aac_uam_bank_build", "aac_uam_get_state",
            "aac_uam_set_state", "aac_uam_actor", "aac_uam_actor_last_error", "aac_uam_set_reset_compact",
-           "aac_uam_use_episode_buffer", "aac_uam_set_terms_buffer")
+           "aac_uam_use_episode_buffer", "aac_uam_set_terms_buffer", "aac_uam_reward_map")
 
 
 class UamCfg(ctypes.Structure):
@@ -443,7 +443,15 @@ class env_simulator:
     def ss_reward_Mar_changeskin(self, current_ts, step_reward_record, step_collision_record, xy=(None, None),
                                  full_observable_critic_flag=False, args=None, evaluation_by_episode=True,
                                  evaluation_by_fixed_ar=False):
-        """UAM/env:3892 -- the kernel's reward / done / check_goal / bbc of the last step."""
+        """UAM/env:3892 -- the kernel's reward / done / check_goal / bbc of the last step.
+
+        ``xy=(x, y)``: the reference's map mode (UAM/env:3939-3944) -- aircraft 0 alone evaluated at (x, y)
+        with ``pre_pos = pos = xy``, as a one-row reward map (``rewardmap.UamRewardMap``): ``reward`` and
+        ``done`` of length 1, ``check_goal`` of length N with entry 0 set, ``step_reward_record[0]``
+        updated.  Unlike the reference's, the call leaves ``all_agents[0].pos`` and the device state as
+        they were."""
+        if xy is not None and xy[0] is not None and xy[1] is not None:
+            return self._ss_reward_at(xy, step_reward_record, step_collision_record)
         last = self._last
         N = self._env.N
         mask = last["mask"]
@@ -470,6 +478,21 @@ class env_simulator:
                 step_reward_record[i] = [0, float(reward[i])]
         bbc = [bool(v) for v in last["bbc"]]
         return reward, done, check_goal, step_reward_record, eps_status_holder, step_collision_record, bbc
+
+    def _ss_reward_at(self, xy, step_reward_record, step_collision_record):
+        """``ss_reward_Mar_changeskin`` in map mode: one reward-map row of aircraft 0 at ``xy`` (``pre = point``,
+        the radar minimum from the held radar row as in the reference, ``prev2`` the live top2)."""
+        if getattr(self, "_rmap", None) is None:
+            from .rewardmap import UamRewardMap
+            self._rmap = UamRewardMap.for_uam(self._env)
+        self._rmap.at(np.array([[float(xy[0]), float(xy[1])]]), rmin=self._rmap.held_rmin())
+        row = self.last_map_row = {k: v[0] for k, v in self._rmap.read().items()}
+        check_goal = [False] * self._env.N
+        check_goal[0] = bool(row["mask"] & 16)
+        if step_reward_record is not None:
+            step_reward_record[0] = [0, float(row["reward"])]
+        return ([np.array(float(row["reward"]))], [bool(row["done"])], check_goal, step_reward_record,
+                [{} for _ in range(self._env.N)], step_collision_record, [bool(v) for v in row["bbc"]])
 
     def episode_over(self, step, episode_length=150):
         """UAM/main:624-637 with ``step`` the already-incremented step counter."""
