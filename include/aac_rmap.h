@@ -10,7 +10,8 @@
  * removed-waypoint bits (WGRU) and start; the other agents' positions; the env's map of the stack.
  * The variant is the handle's: the ATT reward of the step's phase 3-4 (ATT/env:2133-2603: event,
  * progress, near-drone penalty) or the WGRU reward (WGRU/env:1666-2039: waypoint search, progress to the
- * found waypoint, cross-track, small-step and near-building penalties).
+ * found waypoint, cross-track, small-step and near-building penalties).  Both are the step kernel's own
+ * device functions, compiled for the map with their state writes left out.
  *
  * WGRU near-building penalty: with rmin NULL the launch computes the 18-ray obstacle radar at the point,
  * its threshold-band rays decided exactly (as the band fix and aac_env_probe do), so the minimum is the

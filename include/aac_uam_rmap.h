@@ -8,6 +8,8 @@
  * stood at points[m] with pre_pos = pre[m] (pre NULL: pre_pos = points[m], the reference's map mode).
  * Everything else is the handle's live state: the subject's vel, goal, start and reach; the other
  * aircraft's pos and reach; the env's two cloud centres as they stand (no drift); the bound, the runway.
+ * Phase 5 after the neighbour walk is the step kernel's own device function (phase5_tail); the neighbour
+ * scan, the radar and the single-aircraft phase 6 are the map's.
  *
  *   radar      rmin NULL: the 18-ray fp64 radar at the point (ray length, runway, the four bound segments,
  *              both clouds, the N - 1 other aircraft), the step kernel's functions in its expression order:

@@ -613,9 +613,17 @@ __device__ inline double wgru_nbp(double rmin, double pb) {
     return (rmin >= pb && rmin <= 5) ? 3 * (((0 - 1) / (5 - pb)) * rmin + 2) : 0;
 }
 
+// the reward from rp, the reward before its near-building penalty term, and how the term enters
+// (RewFix.kind): wgru_reward's branches, and band_fix_kernel again once rmin is the exact one
+__device__ inline double wgru_with_nbp(int kind, double rp, double nbp) {
+    return kind == 0 ? rp : (kind == 1 ? rp - nbp : (rp - nbp) + 0.0);
+}
+
 // rp, rk: the reward before its penalty term and how the term enters (RewFix)
 // TERMS: the taken branch's terms and the gauges go to the agent's row trow (include/aac_terms.h)
-template <bool TERMS>
+// WRITE: the step's form; false (the reward map) leaves the popped waypoint and the goal rewrite out, so
+// nothing of A is written and ai is not used
+template <bool TERMS, bool WRITE = true>
 __device__ __attribute__((always_inline)) double wgru_reward(const Args &A, size_t ai, WpView wp, double2 pp, double2 p, double2 v, uint32_t rm,
                               int cnt, double rmin, int goal, int bnd, int building, int &flag, int &done, int &cg,
                               uint8_t &fl, double2 start, double &rp, int &rk, double *trow) {
@@ -664,17 +672,19 @@ __device__ __attribute__((always_inline)) double wgru_reward(const Args &A, size
             }
         }
     }
-    if (rm != rm0) {
-        A.wp_cur[ai] = (int32_t)rm;
-        for (int k = cnt - 1; k >= 0; --k)      // goal[-1] after the pop
-            if (!((rm >> k) & 1u)) {
-                A.goal[ai] = wp[k];
-                break;
-            }
+    if constexpr (WRITE) {
+        if (rm != rm0) {
+            A.wp_cur[ai] = (int32_t)rm;
+            for (int k = cnt - 1; k >= 0; --k)      // goal[-1] after the pop
+                if (!((rm >> k) & 1u)) {
+                    A.goal[ai] = wp[k];
+                    break;
+                }
+        }
     }
     const double dafter = npnorm(px - nx.x, py - nx.y);
     const double dtg = 1 * (npnorm(pp.x - nx.x, pp.y - nx.y) - dafter);
-    ASTAMP(6);
+    if constexpr (WRITE) ASTAMP(6);
     // cross_track_error (WGRU/env:2621-2632): nearest point of the first segment at the smallest
     // pointToSegment distance, then the point distance to it.  A segment whose bounding box lies
     // farther than the current best (squared, 1e-8 relative margin) cannot be strictly nearer: its
@@ -726,8 +736,8 @@ __device__ __attribute__((always_inline)) double wgru_reward(const Args &A, size
     double r;
     if (bnd) {
         rp = ((((0.0 + dref) - 5) + dtg) - ssp) + 0.0;
-        r = rp - nbp;
         rk = 1;
+        r = wgru_with_nbp(rk, rp, nbp);
         done = 1;
         fl |= 8;
         if constexpr (TERMS) store_terms(trow, -5.0, 0.0, dref, dtg, -ssp, -nbp, 0.0, cross, sp, dafter, rmin);
@@ -735,25 +745,143 @@ __device__ __attribute__((always_inline)) double wgru_reward(const Args &A, size
         done = 1;
         fl |= 16;
         rp = ((((0.0 + dref) - 5) + dtg) - ssp) + 0.0;
-        r = rp - nbp;
         rk = 1;
+        r = wgru_with_nbp(rk, rp, nbp);
         if constexpr (TERMS) store_terms(trow, -5.0, 0.0, dref, dtg, -ssp, -nbp, 0.0, cross, sp, dafter, rmin);
     } else if (goal) {
         cg = 1;
-        r = rp = (0.0 + 5) + 0.0;
+        rp = (0.0 + 5) + 0.0;
         rk = 0;
+        r = wgru_with_nbp(rk, rp, nbp);
         if constexpr (TERMS) store_terms(trow, 5.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, cross, sp, dafter, rmin);
     } else {
         r = 0.0;
         if (flag && nrem > 1) r = r + 3;
         if constexpr (TERMS) store_terms(trow, 0.0, r, dref, dtg, -ssp, -nbp, 0.0, cross, sp, dafter, rmin);
         rp = (((r + dref) + dtg) - ssp) + 0.0;
-        r = (rp - nbp) + 0.0;
         rk = 2;
+        r = wgru_with_nbp(rk, rp, nbp);
     }
     return r;
 }
 
+
+// ------------------------------------------------ ss_reward's agent phase (ATT/env:2133-2603), step and reward map
+// The predicates and the ATT reward of agent i standing at (px, py).  pos: its env's N positions, the step's
+// LDS copy or the map's rows in global memory (entry i is skipped: the subject stands at the point).
+struct Contacts {
+    int ncoll, last_coll, nearest;
+    double shortest;
+};
+__device__ __attribute__((always_inline)) Contacts drone_contacts(const double2 *pos, int N, int i, double px, double py, double pb) {
+    int ncoll = 0, last_coll = -1, nearest = -1;
+    double shortest = INFINITY;
+    for (int j = 0; j < N; ++j) {
+        if (j == i) continue;
+        const double2 q = pos[j];
+        double d = npnorm(px - q.x, py - q.y);
+        if (d < shortest) {
+            shortest = d;
+            nearest = j;
+        }
+        if (d <= pb * 2) {
+            ++ncoll;
+            last_coll = j;
+        }
+    }
+    return Contacts{ncoll, last_coll, nearest, shortest};
+}
+
+// ATT's near-drone penalty: every other agent within [2.5, 10] adds the term of the shortest distance
+__device__ __attribute__((always_inline)) double drone_penalty(const double2 *pos, int N, int i, double px, double py, double shortest) {
+    const double c_drone = 1 + (2.5 / (10 - 2.5)), m_drone = (0 - 1) / (10 - 2.5);
+    double pen = 0;
+    for (int j = 0; j < N; ++j) {
+        if (j == i) continue;
+        const double2 q = pos[j];
+        double d = npnorm(px - q.x, py - q.y);
+        if (d >= 2.5 && d <= 10) pen = pen + (1 * (m_drone * shortest + c_drone));
+        else pen = pen + 0;
+    }
+    return pen;
+}
+
+// the agent's 64-gon meets an occupied cell: the 3x3 cells around the point's cell of the map occ
+template <bool COLD>
+__device__ __attribute__((always_inline)) int building_scan(const Args &A, const uint8_t *occ, double px, double py) {
+    int building = 0;
+    int ci = (int)floor((px - A.gx0) / 10.0 + 0.5), cj = (int)floor((py - A.gy0) / 10.0 + 0.5);
+    for (int ii = ci - 1; ii <= ci + 1 && !building; ++ii)
+        for (int jj = cj - 1; jj <= cj + 1; ++jj) {
+            if (ii < 0 || jj < 0 || ii >= A.gw || jj >= A.gh) continue;
+            if (!occ[ii * A.gh + jj]) continue;
+            if (building_hit<COLD>(px, py, A.gx0 + 10.0 * ii, A.gy0 + 10.0 * jj, A.pb)) {
+                building = 1;
+                break;
+            }
+        }
+    return building;
+}
+
+// ss_reward of one ATT agent (ATT/env:2266-2603): next waypoint w0 in range, progress toward goal[-1] = g,
+// the branch taken with its done / cg / fl bits (8 bound, 16 drone contact, 32 last contact == nearest)
+// TERMS: the taken branch's terms and gauges 9, 10 go to the row trow (include/aac_terms.h)
+// WRITE: the step's form; false (the reward map) leaves the waypoint advance out, so nothing of A is written
+template <bool TERMS, bool WRITE = true>
+__device__ __attribute__((always_inline)) double att_reward(const Args &A, size_t ai, double2 pp, double px, double py, double2 v, double2 g,
+                                                            double2 w0, int cur, int wcnt, int ncoll, int last_coll, int nearest,
+                                                            double pen, int goal, int bnd, int &wpf, int &done, int &cg,
+                                                            uint8_t &fl, double *trow) {
+    wpf = gdist(px, py, w0.x, w0.y) < 5;
+    const double before = npnorm(pp.x - g.x, pp.y - g.y);
+    const double after = npnorm(px - g.x, py - g.y);
+    const double dtg = (1 * (before - after)) / A.vmax;
+    double r;
+    if (bnd) {
+        r = ((0.0 - 20) - 0.0) - 0;
+        done = 1;
+        fl |= 8;
+    } else if (ncoll > 0) {
+        r = ((0.0 - 20) - 0.0) - pen;
+        done = 1;
+        fl |= 16;
+        if (last_coll == nearest) fl |= 32;
+    } else if (goal) {
+        r = (0.0 + 20) + 0.0;
+        cg = 1;
+    } else {
+        if constexpr (WRITE) {
+            if (wpf && wcnt - cur > 1) {
+                A.wp_cur[ai] = cur + 1;
+                A.wp0[ai] = A.wp[ai * A.W + cur + 1];
+            }
+        }
+        r = dtg - pen;
+    }
+    if constexpr (TERMS) {
+        const bool crash = bnd || ncoll > 0, normal = !crash && !goal;
+        store_terms(trow, crash ? -20.0 : (goal ? 20.0 : 0.0), 0.0, 0.0, normal ? dtg : 0.0, 0.0, 0.0,
+                    (!bnd && ncoll > 0) || normal ? -pen : 0.0, 0.0, npnorm(v.x, v.y), after, 0.0);
+    }
+    return r;
+}
+
+// the agent's mask byte: bound, drone contact, goal, building, waypoint in range, goal branch taken
+__device__ inline uint8_t reward_mask(int bnd, int ncoll, int goal, int building, int wpf, int cg) {
+    uint8_t m = (uint8_t)(bnd | ((ncoll > 0) << 1) | (goal << 2) | (building << 3) | (wpf << 4));
+    if (cg) m |= 32;
+    return m;
+}
+
+// bound_building_check from the fl bits 8 / 16 / 32 of one agent, or of an env's agents or-ed: ATT [bound,
+// 0, drone, last contact == nearest]; variant 1 [bound, building] (WGRU/env:1956, :1963)
+__device__ inline void store_bbc(uint8_t *bbc, int variant, uint8_t fl) {
+    const uint8_t b0 = (fl >> 3) & 1, b2 = (fl >> 4) & 1, b3 = (fl >> 5) & 1;
+    bbc[0] = b0;
+    bbc[1] = variant ? b2 : 0;
+    bbc[2] = variant ? 0 : b2;
+    bbc[3] = variant ? 0 : b3;
+}
 
 // copy n floats from LDS to global memory with 16-B stores where the destination allows
 __device__ inline void store_rows(float *dst, const float *src, int n) {
@@ -1181,7 +1309,7 @@ __device__ __attribute__((always_inline)) void band_fix_body(const FixArgs &F) {
             rmin = d < rmin ? d : rmin;
         }
         const double nbp = wgru_nbp(rmin, F.pb);
-        const double rew = x.kind == 0 ? x.rp : (x.kind == 1 ? x.rp - nbp : (x.rp - nbp) + 0.0);
+        const double rew = wgru_with_nbp(x.kind, x.rp, nbp);
         F.reward[(size_t)x.e * F.N + x.i] = (float)rew;
         if (F.ring && x.row >= 0) F.ring[x.row * F.rw + F.rcol + x.i] = (float)rew;
         if (F.terms) {      // the sum of the row's slots stays the rewritten reward
@@ -1365,44 +1493,12 @@ __global__ void __launch_bounds__(BLOCK, AAC_ENV_MIN_WAVES) step_kernel(Args Ain
 
         // ---- ss_reward (ATT/env:2133-2603)
         const double px = np.x, py = np.y, pb = A.pb;
-        int ncoll = 0, last_coll = -1, nearest = -1;
-        double shortest = INFINITY;
-        for (int j = 0; j < N; ++j) {
-            if (j == i) continue;
-            const double2 q = S.pos[base + j];
-            double d = npnorm(px - q.x, py - q.y);
-            if (d < shortest) {
-                shortest = d;
-                nearest = j;
-            }
-            if (d <= pb * 2) {
-                ++ncoll;
-                last_coll = j;
-            }
-        }
-        const double c_drone = 1 + (2.5 / (10 - 2.5)), m_drone = (0 - 1) / (10 - 2.5);
-        double pen = 0;
-        for (int j = 0; j < N && !A.variant; ++j) {
-            if (j == i) continue;
-            const double2 q = S.pos[base + j];
-            double d = npnorm(px - q.x, py - q.y);
-            if (d >= 2.5 && d <= 10) pen = pen + (1 * (m_drone * shortest + c_drone));
-            else pen = pen + 0;
-        }
+        const Contacts ct = drone_contacts(S.pos + base, N, i, px, py, pb);
+        const int ncoll = ct.ncoll, last_coll = ct.last_coll, nearest = ct.nearest;
+        const double shortest = ct.shortest;
+        const double pen = A.variant ? 0.0 : drone_penalty(S.pos + base, N, i, px, py, shortest);
         ASTAMP(2);
-        int building = 0;
-        {
-            int ci = (int)floor((px - A.gx0) / 10.0 + 0.5), cj = (int)floor((py - A.gy0) / 10.0 + 0.5);
-            for (int ii = ci - 1; ii <= ci + 1 && !building; ++ii)
-                for (int jj = cj - 1; jj <= cj + 1; ++jj) {
-                    if (ii < 0 || jj < 0 || ii >= A.gw || jj >= A.gh) continue;
-                    if (!occ[ii * A.gh + jj]) continue;
-                    if (building_hit<EXACT_COLD(VAR)>(px, py, A.gx0 + 10.0 * ii, A.gy0 + 10.0 * jj, pb)) {
-                        building = 1;
-                        break;
-                    }
-                }
-        }
+        const int building = building_scan<EXACT_COLD(VAR)>(A, occ, px, py);
         if (building) A.wall[ai] += 1;
         ASTAMP(3);
         const double2 g = S.goal[t];
@@ -1420,10 +1516,6 @@ __global__ void __launch_bounds__(BLOCK, AAC_ENV_MIN_WAVES) step_kernel(Args Ain
             r = wgru_reward<TERMS>(A, ai, wv, pp, np, S.vel[t], (uint32_t)cur, wcnt,
                                    __longlong_as_double((long long)S.rmin[t]), goal, bnd, building, wpf, done, cg, fl,
                                    st0, rp, rk, TERMS ? A.terms + ai * AAC_TERMS_W : nullptr);
-            if (cg) {
-                reach = 1;
-                A.reach[ai] = 1;
-            }
             if (fixr && A.rfix) {      // a ray of this agent is decided exactly after the launch: so is rmin
                 const int slot = atomicAdd(A.band_cnt + 2, 1);
                 if (slot < A.band_cap) {
@@ -1436,47 +1528,18 @@ __global__ void __launch_bounds__(BLOCK, AAC_ENV_MIN_WAVES) step_kernel(Args Ain
                 }
             }
         } else {
-            // ATT/env:2266-2603: next waypoint in range, progress toward goal[-1]
-            wpf = gdist(px, py, w0.x, w0.y) < 5;
-            const double before = npnorm(pp.x - g.x, pp.y - g.y);
-            const double after = npnorm(px - g.x, py - g.y);
-            const double dtg = (1 * (before - after)) / A.vmax;
-            if (bnd) {
-                r = ((0.0 - 20) - 0.0) - 0;
-                done = 1;
-                fl |= 8;
-            } else if (ncoll > 0) {
-                r = ((0.0 - 20) - 0.0) - pen;
-                done = 1;
-                fl |= 16;
-                if (last_coll == nearest) fl |= 32;
-            } else if (goal) {
-                r = (0.0 + 20) + 0.0;
-                cg = 1;
-                reach = 1;
-                A.reach[ai] = 1;
-            } else {
-                if (wpf && wcnt - cur > 1) {
-                    A.wp_cur[ai] = cur + 1;
-                    A.wp0[ai] = A.wp[ai * A.W + cur + 1];
-                }
-                r = dtg - pen;
-            }
-            if constexpr (TERMS) {      // the taken branch's terms (include/aac_terms.h), gauges 9 and 10
-                const double2 v = S.vel[t];
-                const bool crash = bnd || ncoll > 0, normal = !crash && !goal;
-                store_terms(A.terms + ai * AAC_TERMS_W, crash ? -20.0 : (goal ? 20.0 : 0.0), 0.0, 0.0,
-                            normal ? dtg : 0.0, 0.0, 0.0, (!bnd && ncoll > 0) || normal ? -pen : 0.0, 0.0,
-                            npnorm(v.x, v.y), after, 0.0);
-            }
+            r = att_reward<TERMS>(A, ai, pp, px, py, S.vel[t], g, w0, cur, wcnt, ncoll, last_coll, nearest, pen, goal, bnd, wpf,
+                                  done, cg, fl, TERMS ? A.terms + ai * AAC_TERMS_W : nullptr);
         }
-        uint8_t m = (uint8_t)(bnd | ((ncoll > 0) << 1) | (goal << 2) | (building << 3) | (wpf << 4));
-        if (cg) m |= 32;
+        if (cg) {
+            reach = 1;
+            A.reach[ai] = 1;
+        }
         fl |= (uint8_t)(done | (cg << 1) | (reach << 2));
         S.rew[t] = r;
         S.flags[t] = fl;
         A.done[ai] = (uint8_t)done;
-        A.mask[ai] = m;
+        A.mask[ai] = reward_mask(bnd, ncoll, goal, building, wpf, cg);
         ASTAMP(5);
     }
     aacw::lds_barrier();
@@ -1511,22 +1574,16 @@ __global__ void __launch_bounds__(BLOCK, AAC_ENV_MIN_WAVES) step_kernel(Args Ain
             }
         }
         if (i == 0) {
-            int any_done = 0, all_goal = 1, all_reach = 1, b0 = 0, b2 = 0, b3 = 0;
+            int any_done = 0, all_goal = 1, all_reach = 1;
+            uint8_t fo = 0;
             for (int j = 0; j < N; ++j) {
                 uint8_t f = S.flags[base + j];
                 any_done |= f & 1;
                 all_goal &= (f >> 1) & 1;
                 all_reach &= (f >> 2) & 1;
-                b0 |= (f >> 3) & 1;
-                b2 |= (f >> 4) & 1;
-                b3 |= (f >> 5) & 1;
+                fo |= f;
             }
-            // ATT: [bound, 0, drone, last contact == nearest]; variant 1: bound_building_check
-            // [bound, building] (WGRU/env:1956, :1963)
-            A.bbc[4 * e + 0] = (uint8_t)b0;
-            A.bbc[4 * e + 1] = (uint8_t)(A.variant ? b2 : 0);
-            A.bbc[4 * e + 2] = (uint8_t)(A.variant ? 0 : b2);
-            A.bbc[4 * e + 3] = (uint8_t)(A.variant ? 0 : b3);
+            store_bbc(A.bbc + 4 * e, A.variant, fo);
             int st = A.step[e] + 1;
             A.step[e] = st;
             const uint8_t ed = (uint8_t)((A.episode_length < st) || any_done || all_goal || all_reach);
@@ -1728,8 +1785,9 @@ __global__ void __launch_bounds__(BLOCK) radar_probe_kernel(ProbeArgs P) {
 // points[m] with pre_pos pre[m], everything else the handle's live state.  One lane per row; the lane
 // reads the subject's state and its env's other agents from global memory (L2: the rows of a sweep share
 // them) and writes nothing but the row's outputs.  The predicates and the arithmetic are the step
-// kernel's (phase 3-4 for ATT, wgru_reward for WGRU), restated without their state writes: no waypoint
-// pop, no reach / wall update, no goal rewrite, no band or fix-up list entry.
+// kernel's own functions (drone_contacts, drone_penalty, building_scan, att_reward / wgru_reward,
+// reward_mask, store_bbc), the reward ones instantiated with WRITE = false: no waypoint pop or advance, no
+// goal rewrite; reach / wall and the band and fix-up lists are written by step_kernel itself, not here.
 struct RmapArgs {
     int64_t M;
     const double *points, *pre;            // [M][2]; pre null: pre_pos = the point
@@ -1740,110 +1798,6 @@ struct RmapArgs {
 };
 static_assert(sizeof(aac_rmap_out) == AAC_RMAP_OUT_BYTES, "the header's constant for bindings");
 #define RMAP_BLOCK 64     // one wave per workgroup: a 2 500-row sweep spreads over 40 CUs
-
-// wgru_reward without its writes: the waypoint search works on a private copy of the removed-waypoint
-// bits, the waypoints come from global memory.  t: the row's 12 terms (include/aac_terms.h)
-__device__ __attribute__((noinline)) double wgru_reward_ro(const Args &A, const double2 *wp, double2 pp, double2 p, double2 v,
-                                                          uint32_t rm, int cnt, double rmin, int goal, int bnd,
-                                                          int building, int &flag, int &done, int &cg, uint8_t &fl,
-                                                          double2 start, double *t) {
-    const double px = p.x, py = p.y, pb = A.pb;
-    int nrem = cnt - __popc(rm & (cnt >= 32 ? 0xffffffffu : ((1u << cnt) - 1u)));
-    double smallest = INFINITY;
-    double2 nx = make_double2(0.0, 0.0);
-    for (int k = 0; k < cnt; ++k) {
-        if ((rm >> k) & 1u) continue;
-        const double2 w = wp[k];
-        const double d = gdist(px, py, w.x, w.y);
-        if (d < smallest) {
-            smallest = d;
-            nx = w;
-            if (smallest < 5) {
-                flag = 1;
-                if (nrem > 1) {
-                    rm |= 1u << k;
-                    --nrem;
-                    double best = INFINITY;
-                    for (int q = 0; q < cnt; ++q) {
-                        if ((rm >> q) & 1u) continue;
-                        const double2 uq = wp[q];
-                        const double dd = gdist(uq.x, uq.y, px, py);
-                        if (dd < best) {
-                            best = dd;
-                            nx = uq;
-                        }
-                    }
-                }
-                break;
-            }
-        }
-    }
-    const double dafter = npnorm(px - nx.x, py - nx.y);
-    const double dtg = 1 * (npnorm(pp.x - nx.x, pp.y - nx.y) - dafter);
-    // cross_track_error (WGRU/env:2621-2632), with wgru_reward's bounding-box skip
-    double cross;
-    {
-        double best = INFINITY;
-        double2 a = start, q = a;
-        for (int k = 0; k < cnt; ++k) {
-            const double2 b = wp[k];
-            {
-                const double ox = fmax(fmax(fmin(a.x, b.x) - px, px - fmax(a.x, b.x)), 0.0);
-                const double oy = fmax(fmax(fmin(a.y, b.y) - py, py - fmax(a.y, b.y)), 0.0);
-                if (ox * ox + oy * oy > best * best * (1.0 + 1e-8)) {
-                    a = b;
-                    continue;
-                }
-            }
-            const double d = point_to_segment(px, py, a.x, a.y, b.x, b.y);
-            if (d < best) {
-                best = d;
-                q = segment_closest_point(px, py, a.x, a.y, b.x, b.y);
-            }
-            if (best <= 0.0) break;
-            a = b;
-        }
-        cross = gdist(px, py, q.x, q.y);
-    }
-    double dref;
-    if (cross <= pb) dref = 3 * (((0 - 1) / (pb - 0)) * cross + 1);
-    else dref = -3 * 1;
-    const double thr = 2 * pb;
-    const double sp = npnorm(v.x, v.y);
-    const double clip = sp < 0 ? 0 : (sp > thr ? thr : sp);
-    const double ssp = 3 * ((thr - clip) * (1.0 / thr));
-    const double nbp = wgru_nbp(rmin, pb);
-    for (int k = 0; k < AAC_TERMS_W; ++k) t[k] = 0.0;
-    t[8] = cross;
-    t[9] = sp;
-    t[10] = dafter;
-    t[11] = rmin;
-    double r;
-    if (bnd || building) {
-        done = 1;
-        fl |= bnd ? 8 : 16;
-        r = (((((0.0 + dref) - 5) + dtg) - ssp) + 0.0) - nbp;
-        t[0] = -5.0;
-        t[2] = dref;
-        t[3] = dtg;
-        t[4] = -ssp;
-        t[5] = -nbp;
-    } else if (goal) {
-        cg = 1;
-        r = (0.0 + 5) + 0.0;
-        t[0] = 5.0;
-    } else {
-        r = 0.0;
-        if (flag && nrem > 1) r = r + 3;
-        t[1] = r;
-        t[2] = dref;
-        t[3] = dtg;
-        t[4] = -ssp;
-        t[5] = -nbp;
-        r = ((((r + dref) + dtg) - ssp) + 0.0 - nbp) + 0.0;
-    }
-    return r;
-}
 
 template <int VAR>
 __global__ void __launch_bounds__(RMAP_BLOCK) reward_map_kernel(Args A, RmapArgs Q) {
@@ -1866,49 +1820,17 @@ __global__ void __launch_bounds__(RMAP_BLOCK) reward_map_kernel(Args A, RmapArgs
     const double2 *pos = A.pos + (size_t)e * N;
 
     // ---- ss_reward's predicates, as step_kernel's agent phase forms them
-    int ncoll = 0, last_coll = -1, nearest = -1;
-    double shortest = INFINITY;
-    for (int j = 0; j < N; ++j) {
-        if (j == i) continue;
-        const double2 q = pos[j];
-        double d = npnorm(px - q.x, py - q.y);
-        if (d < shortest) {
-            shortest = d;
-            nearest = j;
-        }
-        if (d <= pb * 2) {
-            ++ncoll;
-            last_coll = j;
-        }
-    }
-    const double c_drone = 1 + (2.5 / (10 - 2.5)), m_drone = (0 - 1) / (10 - 2.5);
-    double pen = 0;
-    for (int j = 0; j < N && !VAR; ++j) {
-        if (j == i) continue;
-        const double2 q = pos[j];
-        double d = npnorm(px - q.x, py - q.y);
-        if (d >= 2.5 && d <= 10) pen = pen + (1 * (m_drone * shortest + c_drone));
-        else pen = pen + 0;
-    }
-    int building = 0;
-    {
-        int ci = (int)floor((px - A.gx0) / 10.0 + 0.5), cj = (int)floor((py - A.gy0) / 10.0 + 0.5);
-        for (int ii = ci - 1; ii <= ci + 1 && !building; ++ii)
-            for (int jj = cj - 1; jj <= cj + 1; ++jj) {
-                if (ii < 0 || jj < 0 || ii >= A.gw || jj >= A.gh) continue;
-                if (!occ[ii * A.gh + jj]) continue;
-                if (building_hit<EXACT_COLD(VAR)>(px, py, A.gx0 + 10.0 * ii, A.gy0 + 10.0 * jj, pb)) {
-                    building = 1;
-                    break;
-                }
-            }
-    }
+    const Contacts ct = drone_contacts(pos, N, i, px, py, pb);
+    const int ncoll = ct.ncoll, last_coll = ct.last_coll, nearest = ct.nearest;
+    const double shortest = ct.shortest;
+    const double pen = VAR ? 0.0 : drone_penalty(pos, N, i, px, py, shortest);
+    const int building = building_scan<EXACT_COLD(VAR)>(A, occ, px, py);
     const int goal = goal_reached<EXACT_COLD(VAR)>(px, py, g.x, g.y, pb);
     const int bnd = bound_crash(A, pp.x, pp.y, px, py);
     int done = 0, cg = 0, wpf = 0;
     uint8_t fl = 0;
     double r;
-    double t[AAC_TERMS_W];
+    alignas(16) double t[AAC_TERMS_W];      // the terms row, as store_terms fills it
     if (VAR) {
         double rmin;
         if (Q.rmin) {
@@ -1922,49 +1844,19 @@ __global__ void __launch_bounds__(RMAP_BLOCK) reward_map_kernel(Args A, RmapArgs
                 rmin = d < rmin ? d : rmin;
             }
         }
-        r = wgru_reward_ro(A, A.wp + ai * A.W, pp, make_double2(px, py), v, (uint32_t)cur, wcnt, rmin, goal, bnd, building,
-                           wpf, done, cg, fl, A.start[ai], t);
+        const double2 *wp = A.wp + ai * A.W;
+        double rp;
+        int rk;
+        r = wgru_reward<true, false>(A, ai, WpView{wp, wp}, pp, make_double2(px, py), v, (uint32_t)cur, wcnt, rmin, goal,
+                                     bnd, building, wpf, done, cg, fl, A.start[ai], rp, rk, t);
     } else {
-        const double2 w0 = A.wp0[ai];
-        wpf = gdist(px, py, w0.x, w0.y) < 5;
-        const double before = npnorm(pp.x - g.x, pp.y - g.y);
-        const double after = npnorm(px - g.x, py - g.y);
-        const double dtg = (1 * (before - after)) / A.vmax;
-        if (bnd) {
-            r = ((0.0 - 20) - 0.0) - 0;
-            done = 1;
-            fl |= 8;
-        } else if (ncoll > 0) {
-            r = ((0.0 - 20) - 0.0) - pen;
-            done = 1;
-            fl |= 16;
-            if (last_coll == nearest) fl |= 32;
-        } else if (goal) {
-            r = (0.0 + 20) + 0.0;
-            cg = 1;
-        } else {
-            r = dtg - pen;
-        }
-        const bool crash = bnd || ncoll > 0, normal = !crash && !goal;
-        for (int k = 0; k < AAC_TERMS_W; ++k) t[k] = 0.0;
-        t[0] = crash ? -20.0 : (goal ? 20.0 : 0.0);
-        t[3] = normal ? dtg : 0.0;
-        t[6] = (!bnd && ncoll > 0) || normal ? -pen : 0.0;
-        t[9] = npnorm(v.x, v.y);
-        t[10] = after;
+        r = att_reward<true, false>(A, ai, pp, px, py, v, g, A.wp0[ai], cur, wcnt, ncoll, last_coll, nearest, pen,
+                                    goal, bnd, wpf, done, cg, fl, t);
     }
-    uint8_t mk = (uint8_t)(bnd | ((ncoll > 0) << 1) | (goal << 2) | (building << 3) | (wpf << 4));
-    if (cg) mk |= 32;
     Q.reward[m] = r;
-    Q.mask[m] = mk;
+    Q.mask[m] = reward_mask(bnd, ncoll, goal, building, wpf, cg);
     Q.done[m] = (uint8_t)done;
-    // bound_building_check as this agent alone sets it: ATT [bound, 0, drone, last contact == nearest],
-    // variant 1 [bound, building, 0, 0]
-    const uint8_t b0 = (fl >> 3) & 1, b2 = (fl >> 4) & 1, b3 = (fl >> 5) & 1;
-    Q.bbc[4 * m + 0] = b0;
-    Q.bbc[4 * m + 1] = VAR ? b2 : 0;
-    Q.bbc[4 * m + 2] = VAR ? 0 : b2;
-    Q.bbc[4 * m + 3] = VAR ? 0 : b3;
+    store_bbc(Q.bbc + 4 * m, VAR, fl);      // as this agent alone sets it
     if (Q.terms)
         for (int k = 0; k < AAC_TERMS_W; ++k) Q.terms[(size_t)m * AAC_TERMS_W + k] = t[k];
 }

@@ -697,6 +697,66 @@ __device__ __attribute__((always_inline)) void reset_envs(const UArgs &A, const 
 }
 
 // ------------------------------------------------------------------------------- step
+// Phase 5 of the step after the neighbour walk (UAM/env:4202-4486), for uam_step_kernel and the reward map:
+// progress along the reference line s -> g, the near-drone band of the nearest aircraft (fl bits 0 / 1,
+// ndv), the near-building penalty from the radar minimum mn, the bound crash, the kind ladder (fl bits 2 /
+// 3) and the mask byte.  pos: the env's positions, read at nearest and last only (the step's LDS copy, the
+// map's rows in global memory).  base = (0 + dtg) - nbp, the normal branch's reward before its drone term.
+// TERMS: slots 2-5 and 8-11 of the aircraft's row trow (include/aac_terms.h); phase 6 owns 0, 1, 6 and 7
+struct Phase5 {
+    uint8_t kind, fl, mask;
+    double ndv, base;
+};
+template <bool TERMS>
+__device__ __attribute__((always_inline)) Phase5 phase5_tail(const UArgs &A, const double2 *pos, double px, double py, double ppx,
+                                                             double ppy, double2 g, double2 s, double2 v, int nearest,
+                                                             double shortest, int ncoll, int last, int prev_two, int cloud,
+                                                             int goal, double mn, double *trow) {
+    const double pb = A.pb;
+    // dist_to_goal = 5 (1 - total_length_to_end_of_line(pos, ref_line) / L)  (UAM/env:4202-4208)
+    const double L = gdist(g.x, g.y, s.x, s.y);
+    const double rdx = g.x - s.x, rdy = g.y - s.y;
+    double fr = ((px - s.x) * rdx + (py - s.y) * rdy) / (rdx * rdx + rdy * rdy);
+    fr = fr < 0.0 ? 0.0 : (fr > 1.0 ? 1.0 : fr);
+    const double cross = gdist(px, py, s.x + fr * rdx, s.y + fr * rdy);
+    const double left = cross + (L - fr * L);
+    const double dtg = 5.0 * (1 - (left / L));
+    // near-drone band (UAM/env:4305-4327); near-building penalty (UAM/env:4466-4481)
+    uint8_t fl = 0;
+    double ndv = 0.0;
+    if (nearest >= 0 && shortest >= 2.0 && shortest <= 5.0) {
+        const double2 q = pos[nearest];
+        const double br = bearing(px, py, q.x, q.y);
+        fl |= 1 | ((br >= 90.0 && br <= 180) << 1);
+        ndv = ((0 - 1) / (5.0 - 2.0)) * shortest + (1 + (2.0 / (5.0 - 2.0)));
+    }
+    const double nbp = (mn >= pb && mn <= 5.0) ? 2.0 * (((0 - 1) / (5.0 - pb)) * mn + 2) : 0.0;
+    if constexpr (TERMS) {      // the gauges: every branch writes them
+        double2 *q = reinterpret_cast<double2 *>(trow);
+        q[4] = make_double2(cross, npnorm(v.x, v.y));
+        q[5] = make_double2(npnorm(px - g.x, py - g.y), mn);
+    }
+    const int bnd = capsule_crash(pb, A.bound, ppx, ppy, px, py);
+    uint8_t kind;
+    if (bnd) kind = 0;
+    else if (cloud) kind = 1;
+    else if (ncoll > 0) {
+        kind = 2;
+        const double2 q = pos[last];
+        const double br = bearing(px, py, q.x, q.y);
+        fl |= ((br >= 90.0 && br <= 180) << 2) | (prev_two << 3);
+    } else if (goal) kind = 3;
+    else kind = 4;
+    if constexpr (TERMS) {      // path 0, progress, speed 0, building: the normal branch's, else 0
+        double2 *q = reinterpret_cast<double2 *>(trow);
+        q[1] = make_double2(0.0, kind == 4 ? dtg : 0.0);
+        q[2] = make_double2(0.0, kind == 4 ? -nbp : 0.0);
+    }
+    const uint8_t mask = (uint8_t)(bnd | (cloud << 1) | ((ncoll > 0) << 2) | (goal << 3) | ((kind == 3) << 4) |
+                                   ((kind == 2 && prev_two) << 5));
+    return Phase5{kind, fl, mask, ndv, (0 + dtg) - nbp};
+}
+
 // (the replay push inside this launch was built, bit-exact, and measured slower: the launch grew 188 ->
 // 234 us against the 23-us push launch it replaced; so was the bank reset of the finished envs in it,
 // config 5 226 vs 238 M agent-env-steps/s; round 5, removed in round 6)
@@ -832,56 +892,17 @@ __global__ void __launch_bounds__(BLOCK, AAC_UAM_MIN_WAVES) uam_step_kernel(UArg
                 cloud = gons_meet_band<true>(px, py, c.x, c.y, pb, c_world.radius[k], true);
             }
         }
-        const double2 g = S.goal[t];
-        // dist_to_goal = 5 (1 - total_length_to_end_of_line(pos, ref_line) / L)  (UAM/env:4202-4208)
-        const double2 s = A.start[ai];
-        const double L = gdist(g.x, g.y, s.x, s.y);
-        const double rdx = g.x - s.x, rdy = g.y - s.y;
-        double fr = ((px - s.x) * rdx + (py - s.y) * rdy) / (rdx * rdx + rdy * rdy);
-        fr = fr < 0.0 ? 0.0 : (fr > 1.0 ? 1.0 : fr);
-        const double cross = gdist(px, py, s.x + fr * rdx, s.y + fr * rdy);
-        const double left = cross + (L - fr * L);
-        const double dtg = 5.0 * (1 - (left / L));
-        // near-drone band (UAM/env:4305-4327); near-building penalty (UAM/env:4466-4481)
-        uint8_t fl = 0;
-        double ndv = 0.0;
-        if (nearest >= 0 && shortest >= 2.0 && shortest <= 5.0) {
-            const double2 q = S.pos[base + nearest];
-            const double br = bearing(px, py, q.x, q.y);
-            fl |= 1 | ((br >= 90.0 && br <= 180) << 1);
-            ndv = ((0 - 1) / (5.0 - 2.0)) * shortest + (1 + (2.0 / (5.0 - 2.0)));
-        }
         double mn = S.rad[t][0];
         for (int r = 1; r < NRAY; ++r) mn = S.rad[t][r] < mn ? S.rad[t][r] : mn;
-        const double nbp = (mn >= pb && mn <= 5.0) ? 2.0 * (((0 - 1) / (5.0 - pb)) * mn + 2) : 0.0;
-        if constexpr (TERMS) {      // the gauges: every branch writes them
-            const double2 v = S.vel[t];
-            double2 *q = reinterpret_cast<double2 *>(terms + ai * AAC_TERMS_W);
-            q[4] = make_double2(cross, npnorm(v.x, v.y));
-            q[5] = make_double2(npnorm(px - g.x, py - g.y), mn);
-        }
-        const int bnd = capsule_crash(pb, A.bound, pp.x, pp.y, px, py);
-        uint8_t kind;
-        if (bnd) kind = 0;
-        else if (cloud) kind = 1;
-        else if (ncoll > 0) {
-            kind = 2;
-            const double2 q = S.pos[base + last];
-            const double br = bearing(px, py, q.x, q.y);
-            fl |= ((br >= 90.0 && br <= 180) << 2) | (prev_two << 3);
-        } else if (goal) kind = 3;
-        else kind = 4;
+        const Phase5 p5 = phase5_tail<TERMS>(A, S.pos + base, px, py, pp.x, pp.y, S.goal[t], A.start[ai], S.vel[t], nearest,
+                                             shortest, ncoll, last, prev_two, cloud, goal, mn,
+                                             TERMS ? terms + ai * AAC_TERMS_W : nullptr);
+        const uint8_t kind = p5.kind;
         S.kind[t] = kind;
-        S.flag[t] = fl;
-        S.nd_val[t] = ndv;
-        S.base[t] = (0 + dtg) - nbp;
-        if constexpr (TERMS) {      // path 0, progress, speed 0, building: the normal branch's, else 0
-            double2 *q = reinterpret_cast<double2 *>(terms + ai * AAC_TERMS_W);
-            q[1] = make_double2(0.0, kind == 4 ? dtg : 0.0);
-            q[2] = make_double2(0.0, kind == 4 ? -nbp : 0.0);
-        }
-        A.mask[ai] = (uint8_t)(bnd | (cloud << 1) | ((ncoll > 0) << 2) | (goal << 3) | ((kind == 3) << 4) |
-                               ((kind == 2 && prev_two) << 5));
+        S.flag[t] = p5.fl;
+        S.nd_val[t] = p5.ndv;
+        S.base[t] = p5.base;
+        A.mask[ai] = p5.mask;
         if (kind == 3) S.reach[t] = 1;
         A.reach[ai] = S.reach[t];
     }
@@ -1160,22 +1181,6 @@ __global__ void __launch_bounds__(BLOCK) uam_reward_map_kernel(UArgs A, UMap Q) 
             cloud = gons_meet_band<true>(px, py, c.x, c.y, pb, c_world.radius[k], true);
         }
     }
-    const double2 s = A.start[ai];
-    const double L = gdist(g.x, g.y, s.x, s.y);
-    const double rdx = g.x - s.x, rdy = g.y - s.y;
-    double fr = ((px - s.x) * rdx + (py - s.y) * rdy) / (rdx * rdx + rdy * rdy);
-    fr = fr < 0.0 ? 0.0 : (fr > 1.0 ? 1.0 : fr);
-    const double cross = gdist(px, py, s.x + fr * rdx, s.y + fr * rdy);
-    const double left = cross + (L - fr * L);
-    const double dtg = 5.0 * (1 - (left / L));
-    uint8_t fl = 0;
-    double ndv = 0.0;
-    if (nearest >= 0 && shortest >= 2.0 && shortest <= 5.0) {
-        const double2 q = A.pos[eb + nearest];
-        const double br = bearing(px, py, q.x, q.y);
-        fl |= 1 | ((br >= 90.0 && br <= 180) << 1);
-        ndv = ((0 - 1) / (5.0 - 2.0)) * shortest + (1 + (2.0 / (5.0 - 2.0)));
-    }
     double mn;
     if (Q.rmin) {
         mn = Q.rmin[m];
@@ -1183,50 +1188,32 @@ __global__ void __launch_bounds__(BLOCK) uam_reward_map_kernel(UArgs A, UMap Q) 
         mn = s_rad[lr][0];
         for (int k = 1; k < NRAY; ++k) mn = s_rad[lr][k] < mn ? s_rad[lr][k] : mn;
     }
-    const double nbp = (mn >= pb && mn <= 5.0) ? 2.0 * (((0 - 1) / (5.0 - pb)) * mn + 2) : 0.0;
-    const int bnd = capsule_crash(pb, A.bound, ppx, ppy, px, py);
-    int kind;
-    if (bnd) kind = 0;
-    else if (cloud) kind = 1;
-    else if (ncoll > 0) {
-        kind = 2;
-        const double2 q = A.pos[eb + last];
-        const double br = bearing(px, py, q.x, q.y);
-        fl |= ((br >= 90.0 && br <= 180) << 2) | (prev_two << 3);
-    } else if (goal) kind = 3;
-    else kind = 4;
+    alignas(16) double tr[AAC_TERMS_W];      // the terms row: phase5_tail's slots, then phase 6's
+    const Phase5 p5 = phase5_tail<true>(A, A.pos + eb, px, py, ppx, ppy, g, A.start[ai], A.vel[ai], nearest, shortest, ncoll, last,
+                                        prev_two, cloud, goal, mn, tr);
+    const uint8_t kind = p5.kind, fl = p5.fl;
     // ---- phase 6 with the coefficients of this aircraft alone
     const double ndc = ((fl & 1) && (fl & 2)) ? 2.0 * 2 : 2.0;
     const double crash = (kind == 2 && (fl & 4)) ? 50.0 * 2 : 50.0;
-    const double nd = (fl & 1) ? ndc * ndv : ndc * 0;
+    const double nd = (fl & 1) ? ndc * p5.ndv : ndc * 0;
     double rew;
     if (kind < 3) rew = 0 - crash;
     else if (kind == 3) rew = 0 + 50.0 + 0;
-    else rew = ((0 + dtg) - nbp) - nd;
+    else rew = p5.base - nd;
     Q.reward[m] = rew;
     Q.done[m] = (uint8_t)(kind < 3);
-    Q.mask[m] = (uint8_t)(bnd | (cloud << 1) | ((ncoll > 0) << 2) | (goal << 3) | ((kind == 3) << 4) |
-                          ((kind == 2 && prev_two) << 5));
+    Q.mask[m] = p5.mask;
     Q.flags[m] = fl;
     Q.bbc[4 * m + 0] = kind == 0;
     Q.bbc[4 * m + 1] = kind == 1;
     Q.bbc[4 * m + 2] = kind == 2;
     Q.bbc[4 * m + 3] = kind == 2 && (fl & 8);
     if (Q.terms) {
-        const double2 v = A.vel[ai];
-        double *q = Q.terms + m * AAC_TERMS_W;
-        q[0] = kind < 3 ? -crash : (kind == 3 ? 50.0 : 0.0);
-        q[1] = 0.0;
-        q[2] = 0.0;
-        q[3] = kind == 4 ? dtg : 0.0;
-        q[4] = 0.0;
-        q[5] = kind == 4 ? -nbp : 0.0;
-        q[6] = kind == 4 ? -nd : 0.0;
-        q[7] = 0.0;
-        q[8] = cross;
-        q[9] = npnorm(v.x, v.y);
-        q[10] = npnorm(px - g.x, py - g.y);
-        q[11] = mn;
+        tr[0] = kind < 3 ? -crash : (kind == 3 ? 50.0 : 0.0);
+        tr[1] = 0.0;
+        tr[6] = kind == 4 ? -nd : 0.0;
+        tr[7] = 0.0;
+        for (int k = 0; k < AAC_TERMS_W; ++k) Q.terms[m * AAC_TERMS_W + k] = tr[k];
     }
 }
 

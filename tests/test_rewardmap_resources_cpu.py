@@ -1,8 +1,10 @@
 """Compile-time guard (hipcc, no GPU): the reward map left the env's existing kernels alone.  The map kernel
-restates the step's reward without its state writes and calls the helpers the step, reset, band-fix and probe
-kernels use (``building_hit``, ``goal_reached``, ``bound_crash``, ``radar_ray_exact``); a new caller can change
-what the compiler inlines where, so their VGPR / SGPR / LDS / scratch figures must be the ones the commit
-before the map had, taken with the command of tests/test_probe_resources_cpu.py."""
+calls the step's own reward functions (``att_reward`` / ``wgru_reward`` compiled without their state writes,
+``drone_contacts``, ``building_scan``, ...) and the helpers the step, reset, band-fix and probe kernels use
+(``building_hit``, ``goal_reached``, ``bound_crash``, ``radar_ray_exact``); a second caller and a function
+boundary can change what the compiler inlines and schedules where, so their VGPR / SGPR / LDS / scratch
+figures must be the ones the commit before the map had, taken with the command of
+tests/test_probe_resources_cpu.py."""
 import os
 import shutil
 

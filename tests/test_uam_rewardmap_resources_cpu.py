@@ -1,6 +1,7 @@
 """Resource usage of csrc/aac_uam.hip's kernels with the reward-map kernel in the file, as hipcc reports it for
 gfx950 (the command of tests/test_uam_terms_resources_cpu.py).  ``uam_reward_map_kernel`` shares the step's
-geometry helpers; adding it must leave the step and reset kernels as the commit before it reported them.
+geometry helpers and its phase-5 tail (``phase5_tail``); that must leave the step and reset kernels as the
+commit before the map reported them.
 The new kernel's figures are printed, not bounded (DESIGN.md section 4 records them)."""
 import os
 import shutil
