@@ -5,8 +5,8 @@
  * gradient exists only as split-K partial copies and the update is one captured graph, so the norm and
  * the scaling live in two launches that replace an Adam launch:
  *
- *   aac_clip_sumsq       sums the copies in the Adam kernels' order (writing the sum to grad_out when
- *                        asked), squares gscale * g in double and leaves one partial per workgroup;
+ *   aac_clip_sumsq       sums the copies as the Adam kernels do (csrc/aac_copysum.h holds the sum for
+ *                        both; the sum goes to grad_out when asked), squares gscale * g in double and leaves one partial per workgroup;
  *   aac_adam_flat_clip   every workgroup folds its segment's partials over the same fixed tree (the same
  *                        bits everywhere), forms coef = min(1, max_norm / (sqrt(sum) + 1e-6)) in double,
  *                        rounds it to the element type once and runs the Adam step on (gscale * g) * coef.

@@ -146,6 +146,12 @@ int aac_adam_flat_sum_pair(const aac_adam_job *a, const aac_adam_job *b, void *s
 int aac_sum_partials(float *out, const float *gpart, int32_t nsplit, int64_t n, void *stream);
 int aac_sum_partials_strided(float *out, const float *gpart, int32_t nsplit, int64_t gstride, int64_t n, void *stream);
 
+/* The order in which aac_adam_flat_sum_strided and aac_sum_partials_strided sum these copies: 1 = the
+ * four copy groups s % 4, each in increasing s, then (g0 + g1) + (g2 + g3) (the copy-parallel kernels:
+ * nsplit >= 2, gstride % 4 == 0, 16-B aligned copies, AAC_ADAM4 on), 0 = the copies in sequence.  The
+ * order field of an aac_clip_job / aac_monitor_vec_job that must reproduce their sum.  No launch. */
+int32_t aac_copy_sum_order(const float *gpart, int32_t nsplit, int64_t gstride);
+
 /* Critic output layer + loss gradient, rows of 256 features h[r*ldh + j]:
  *   q[r] = h[r] . w + b[0]
  *   mode 0 (critic loss, mse):  dq = (2/M)(q - y[r])      dh = dq w * (h > 0)

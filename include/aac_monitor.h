@@ -63,7 +63,9 @@ extern "C" {
  * with f64).  The gradient is the sum of ``nsplit`` partial copies ``gstride`` elements apart, formed in
  * the element type: order 0 sums the copies 0, 1, 2, ... in sequence (aac_sum64_partials, aac_adam64_sum
  * and the scalar float Adam); order 1 sums the four groups s % 4 each in sequence and then
- * (g0 + g1) + (g2 + g3) (the copy-parallel float Adam / aac_sum_partials).  The sum is multiplied by
+ * (g0 + g1) + (g2 + g3) (the copy-parallel float Adam / aac_sum_partials; aac_copy_sum_order in
+ * aac_fused.h says which of the two the float kernels take for a set of copies, and
+ * csrc/aac_copysum.h holds both sums for every kernel).  The sum is multiplied by
  * gscale in the element type.  Segment s starts at g + s * seg_stride and param + s * seg_stride and
  * lands in column col0 + s; its AAC_MONITOR_VEC_WG slots of AAC_MONITOR_VEC_VALUES doubles are
  * scratch[((col0 + s) * AAC_MONITOR_NETS + net) * AAC_MONITOR_VEC_WG + w].  Pointers need only the

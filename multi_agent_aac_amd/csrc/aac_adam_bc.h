@@ -1,4 +1,5 @@
-// Adam's bias corrections for the optimiser kernels (aac_fused.hip, aac_learn.hip, aac_uam_learn.hip).
+// Adam's bias corrections and element step for the optimiser kernels (aac_fused.hip, aac_learn.hip,
+// aac_uam_learn.hip, aac_clip.hip).
 //
 // step_size = lr / (1 - b1^t) and bc2s = sqrt(1 - b2^t) are the same two numbers for every thread of
 // a launch, and their double pow / divide / sqrt is some 330 fp64 VALU instructions in one dependent
@@ -32,18 +33,20 @@ __device__ __forceinline__ double adam_bc2_sqrt(double b2, int t) {
     return sqrt(bc2);
 }
 
-// One element's Adam step on gradient gi, for kernels that keep the expression outside their loop
-// (aac_clip.hip): the float form is adam_kernel's (aac_learn.hip; torch's lerp / addcmul / addcdiv
-// order), the double form adam64_kernel's (aac_uam_learn.hip), operation for operation.
+// One element's Adam step on gradient gi: the only place the element arithmetic is written.  Every
+// optimiser kernel calls it -- adam_kernel (aac_learn.hip), adam_sum_kernel and adam4_body
+// (aac_fused.hip), adam64_kernel (aac_uam_learn.hip), adam_clip_kernel (aac_clip.hip) -- so their
+// steps on equal inputs are the same bits.  The float form follows torch's operation order, the
+// double form the UAM learner's b1 * m + (1 - b1) * g.
 __device__ __forceinline__ void adam_elem(float &p, float &m, float &v, float gi, float b1, float b2, float eps,
                                           float step_size, float bc2s) {
     const float w1 = (float)(1.0 - (double)b1), w2 = (float)(1.0 - (double)b2);
     float mi = m;
-    mi = mi + w1 * (gi - mi);
-    float vi = v * b2;
-    vi = vi + w2 * (gi * gi);
+    mi = mi + w1 * (gi - mi);               // exp_avg.lerp_(grad, 1 - beta1)
+    float vi = v * b2;                      // exp_avg_sq.mul_(beta2)
+    vi = vi + w2 * (gi * gi);               //   .addcmul_(grad, grad, 1 - beta2)
     const float den = sqrtf(vi) / bc2s + eps;
-    p = p + (-step_size) * (mi / den);
+    p = p + (-step_size) * (mi / den);      // param.addcdiv_(exp_avg, denom, -step_size)
     m = mi;
     v = vi;
 }

@@ -4,8 +4,9 @@
 //
 // clip_sumsq_kernel      one workgroup per AAC_CLIP_CHUNK elements of a segment (one or two jobs a launch).
 //                        Thread t takes the 16-byte units t, t + 256, ... of the chunk (float: one): the copies summed
-//                        in the element type in the Adam kernels' order (one 16-byte load per copy where
-//                        the segment's copies and grad_out are aligned, scalar loads otherwise -- the same
+//                        in the element type by sum_unit (aac_copysum.h, where the Adam kernels' sums
+//                        live too; one 16-byte load per copy where the segment's copies and grad_out
+//                        are aligned, scalar loads otherwise -- the same
 //                        elements to the same thread either way), the sum stored to grad_out, gscale * g
 //                        squared and accumulated in double.  A butterfly folds each wave, thread 0 the
 //                        four wave results in order: one partial per workgroup, one writer per partial.
@@ -22,6 +23,7 @@
 
 #include "aac_adam_bc.h"
 #include "aac_clip.h"
+#include "aac_copysum.h"
 #include "aac_env.h"
 
 namespace {
@@ -43,82 +45,9 @@ struct ClipArgs {
     int per0, per1;     // workgroups per segment of each job
 };
 
-// V consecutive elements at p (cnt of them exist): one 16-byte load where allowed
-template <typename T, int V>
-__device__ __forceinline__ void load_unit(const T *__restrict__ p, bool wide, int cnt, T (&x)[V]) {
-    typedef T VT __attribute__((ext_vector_type(V)));
-    if (wide) {
-        const VT q = *reinterpret_cast<const VT *>(p);
-#pragma unroll
-        for (int c = 0; c < V; ++c) x[c] = q[c];
-    } else {
-#pragma unroll
-        for (int c = 0; c < V; ++c) x[c] = c < cnt ? p[c] : T(0);
-    }
-}
-
-// the summed gradient of V consecutive elements, in the element type and the Adam kernels' order
-template <typename T, int V>
-__device__ __forceinline__ void sum_unit(const T *__restrict__ g, int ns, int64_t gs, int order, bool wide, int cnt,
-                                         T (&out)[V]) {
-    T x[8][V];
-    if (order == 0) {
-        // copies 0, 1, 2, ... in sequence (eight loads in flight per step)
-        load_unit<T, V>(g, wide, cnt, out);
-        int s = 1;
-        for (; s + 8 <= ns; s += 8) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) load_unit<T, V>(g + (int64_t)(s + u) * gs, wide, cnt, x[u]);
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-#pragma unroll
-                for (int c = 0; c < V; ++c) out[c] += x[u][c];
-        }
-        for (; s < ns; ++s) {
-            load_unit<T, V>(g + (int64_t)s * gs, wide, cnt, x[0]);
-#pragma unroll
-            for (int c = 0; c < V; ++c) out[c] += x[0][c];
-        }
-        return;
-    }
-    // the four copy groups s % 4, each in sequence from zero, then (g0 + g1) + (g2 + g3); eight loads
-    // (two copies of every group) in flight per step
-    T a[4][V];
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int c = 0; c < V; ++c) a[u][c] = T(0);
-    int s = 0;
-    for (; s + 8 <= ns; s += 8) {
-#pragma unroll
-        for (int u = 0; u < 8; ++u) load_unit<T, V>(g + (int64_t)(s + u) * gs, wide, cnt, x[u]);
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-#pragma unroll
-            for (int c = 0; c < V; ++c) a[u & 3][c] += x[u][c];
-    }
-#pragma unroll
-    for (int u = 0; u < 7; ++u) {
-        if (s + u < ns) load_unit<T, V>(g + (int64_t)(s + u) * gs, wide, cnt, x[u]);
-    }
-#pragma unroll
-    for (int u = 0; u < 7; ++u) {
-        if (s + u < ns) {
-#pragma unroll
-            for (int c = 0; c < V; ++c) a[u & 3][c] += x[u][c];
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < V; ++c) out[c] = (a[0][c] + a[1][c]) + (a[2][c] + a[3][c]);
-}
-
-__device__ __forceinline__ unsigned addr16(const void *p) { return (unsigned)((uintptr_t)p & 15u); }
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
+using aaccs::addr16;
+using aaccs::wave_sum;
+constexpr int DEPTH = 8;      // copy loads in flight per step of a unit's sum
 
 template <typename T>
 __global__ __launch_bounds__(NT) void clip_sumsq_kernel(ClipArgs A) {
@@ -128,14 +57,14 @@ __global__ __launch_bounds__(NT) void clip_sumsq_kernel(ClipArgs A) {
     const bool second = (int)blockIdx.x >= A.first;
     const int blk = second ? (int)blockIdx.x - A.first : (int)blockIdx.x, P = second ? A.per1 : A.per0;
     const int seg = blk / P, w = blk % P, t = threadIdx.x;
-    const int64_t n = second ? A.j1.n : A.j0.n, gs = second ? A.j1.gstride : A.j0.gstride;
-    const int64_t sstride = second ? A.j1.seg_stride : A.j0.seg_stride;
-    const int ns = second ? A.j1.nsplit : A.j0.nsplit, order = second ? A.j1.order : A.j0.order;
-    const T gscale = (T)(second ? A.j1.gscale : A.j0.gscale);
-    const T *__restrict__ g = (const T *)(second ? A.j1.g : A.j0.g) + seg * sstride;
-    T *gout = (T *)(second ? A.j1.grad_out : A.j0.grad_out);
+    const aac_clip_job &j = second ? A.j1 : A.j0;
+    const int64_t n = j.n, gs = j.gstride, sstride = j.seg_stride;
+    const int ns = j.nsplit, order = j.order;
+    const T gscale = (T)j.gscale;
+    const T *__restrict__ g = (const T *)j.g + seg * sstride;
+    T *gout = (T *)j.grad_out;
     if (gout) gout += seg * sstride;
-    double *partials = second ? A.j1.partials : A.j0.partials;
+    double *partials = j.partials;
     // 16-byte accesses need every copy of the segment, and grad_out, on the 16-byte grid
     const bool wide = (ns == 1 || (gs * (int64_t)sizeof(T)) % 16 == 0) && addr16(g) == 0 && (!gout || addr16(gout) == 0);
     const int64_t c0 = (int64_t)w * CHUNK, c1 = c0 + CHUNK < n ? c0 + CHUNK : n;
@@ -144,7 +73,7 @@ __global__ __launch_bounds__(NT) void clip_sumsq_kernel(ClipArgs A) {
         const int cnt = c1 - i0 < V ? (int)(c1 - i0) : V;
         const bool full = cnt == V;
         T x[V];
-        sum_unit<T, V>(g + i0, ns, gs, order, wide && full, cnt, x);
+        aaccs::sum_unit<T, V, DEPTH>(g + i0, ns, gs, order, wide && full, cnt, x);
         if (gout) {
             if (wide && full) {
                 VT q;
@@ -182,19 +111,18 @@ __global__ __launch_bounds__(NT) void adam_clip_kernel(ClipArgs A) {
     const bool second = (int)blockIdx.x >= A.first;
     const int blk = second ? (int)blockIdx.x - A.first : (int)blockIdx.x, G = second ? A.per1 : A.per0;
     const int seg = blk / G, b = blk % G, t = threadIdx.x;
-    const int64_t n = second ? A.j1.n : A.j0.n, sstride = second ? A.j1.seg_stride : A.j0.seg_stride;
-    const void *gsum = second ? (A.j1.grad_out ? A.j1.grad_out : A.j1.g) : (A.j0.grad_out ? A.j0.grad_out : A.j0.g);
-    const T *__restrict__ g = (const T *)gsum + seg * sstride;
-    T *p = (T *)(second ? A.j1.param : A.j0.param) + seg * sstride;
-    T *m = (T *)(second ? A.j1.exp_avg : A.j0.exp_avg) + seg * sstride;
-    T *v = (T *)(second ? A.j1.exp_avg_sq : A.j0.exp_avg_sq) + seg * sstride;
-    const T gscale = (T)(second ? A.j1.gscale : A.j0.gscale);
-    const T lr = (T)(second ? A.j1.lr : A.j0.lr), b1 = (T)(second ? A.j1.beta1 : A.j0.beta1);
-    const T b2 = (T)(second ? A.j1.beta2 : A.j0.beta2), eps = (T)(second ? A.j1.eps : A.j0.eps);
-    const double max_norm = second ? A.j1.max_norm : A.j0.max_norm;
-    const int tstep = *(second ? A.j1.step : A.j0.step) + (second ? A.j1.step_add : A.j0.step_add);
+    const aac_clip_job &j = second ? A.j1 : A.j0;
+    const int64_t n = j.n, sstride = j.seg_stride;
+    const T *__restrict__ g = (const T *)(j.grad_out ? j.grad_out : j.g) + seg * sstride;
+    T *p = (T *)j.param + seg * sstride;
+    T *m = (T *)j.exp_avg + seg * sstride;
+    T *v = (T *)j.exp_avg_sq + seg * sstride;
+    const T gscale = (T)j.gscale;
+    const T lr = (T)j.lr, b1 = (T)j.beta1, b2 = (T)j.beta2, eps = (T)j.eps;
+    const double max_norm = j.max_norm;
+    const int tstep = *j.step + j.step_add;
     const int64_t P = (n + CHUNK - 1) / CHUNK;
-    const double *__restrict__ part = (second ? A.j1.partials : A.j0.partials) + (size_t)seg * P;
+    const double *__restrict__ part = j.partials + (size_t)seg * P;
     const int64_t stride = (int64_t)G * NT;
     int64_t i = (int64_t)b * NT + t;
     // the first trip's loads go out ahead of the fold and the bias corrections (clamped index,
@@ -225,7 +153,7 @@ __global__ __launch_bounds__(NT) void adam_clip_kernel(ClipArgs A) {
         g0 = g[i], m0 = m[i], v0 = v[i], p0 = p[i];
     }
     if (b == 0 && t == 0) {
-        double *rec = (second ? A.j1.record : A.j0.record) + (size_t)seg * NR;
+        double *rec = j.record + (size_t)seg * NR;
         rec[AAC_CLIP_R_STEPS] += 1.0;
         if (coefd < 1.0) rec[AAC_CLIP_R_CLIPPED] += 1.0;
         if (!__builtin_isfinite(norm)) rec[AAC_CLIP_R_NONFINITE] += 1.0;

@@ -25,6 +25,7 @@
 #include "../../include/aac_fused.h"
 #include "aac_wave.h"
 #include "aac_adam_bc.h"
+#include "aac_copysum.h"
 
 namespace {
 
@@ -797,26 +798,8 @@ __global__ void __launch_bounds__(256, 5) gemm_kernel(GBatch g) {
 }
 
 // ------------------------------------------------------------------------------ optimiser
-// sum of the ns split-K partial copies of element i, in copy order (so the result does not depend
-// on how the loads are batched): eight independent loads in flight per step instead of a
-// dependent chain of ns
-// (gi: copy 0's value, which a caller may have loaded earlier)
-__device__ __forceinline__ float sum_copies(const float *__restrict__ gpart, int ns, int64_t n, int64_t i, float gi) {
-    int s = 1;
-    for (; s + 8 <= ns; s += 8) {
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = gpart[(int64_t)(s + u) * n + i];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) gi += v[u];
-    }
-    for (; s < ns; ++s) gi += gpart[(int64_t)s * n + i];
-    return gi;
-}
-
-__device__ __forceinline__ float sum_copies(const float *__restrict__ gpart, int ns, int64_t n, int64_t i) {
-    return sum_copies(gpart, ns, n, i, gpart[i]);
-}
+// the copies in sequence (aac_copysum.h, order 0), one element per thread
+using aaccs::copy_sum_seq;
 
 __global__ void adam_sum_kernel(float *p, const float *__restrict__ gpart, int ns, int64_t gs, float *gout, float *m,
                                 float *v, int64_t n, float lr, float b1, float b2, float eps, const int32_t *step, int step_add) {
@@ -831,36 +814,27 @@ __global__ void adam_sum_kernel(float *p, const float *__restrict__ gpart, int n
     const float g0 = gpart[ic];
     float step_size, bc2s;
     adam_bias_bcast(bc, lr, b1, b2, t, step_size, bc2s);
-    float gi = sum_copies(gpart, ns, gs, ic, g0);
-    const float w1 = (float)(1.0 - (double)b1), w2 = (float)(1.0 - (double)b2);
+    float gi = copy_sum_seq(gpart, ns, gs, ic, g0);
     while (i < n) {
         if (gout) gout[i] = gi;
-        float mi = m0;
-        mi = mi + w1 * (gi - mi);               // exp_avg.lerp_(grad, 1 - beta1)
-        float vi = v0 * b2;                     // exp_avg_sq.mul_(beta2)
-        vi = vi + w2 * (gi * gi);               //   .addcmul_(grad, grad, 1 - beta2)
-        const float den = sqrtf(vi) / bc2s + eps;
-        p[i] = p0 + (-step_size) * (mi / den);     // param.addcdiv_(exp_avg, denom, -step_size)
-        m[i] = mi;
-        v[i] = vi;
+        adam_elem(p0, m0, v0, gi, b1, b2, eps, step_size, bc2s);
+        p[i] = p0;
+        m[i] = m0;
+        v[i] = v0;
         i += stride;
         if (i >= n) break;
         m0 = m[i], v0 = v[i], p0 = p[i];
-        gi = sum_copies(gpart, ns, gs, i);
+        gi = copy_sum_seq(gpart, ns, gs, i, gpart[i]);
     }
 }
 
-// Copy-parallel form (copy stride gs % 4 == 0 -- the learners pad it -- and 16-B aligned copies): a
-// wave takes 64 consecutive elements; lane
+// Copy-parallel form of the four-group order (aac_copysum.h, order 1), for copy stride gs % 4 == 0
+// (the learners pad it) and 16-B aligned copies: a wave takes 64 consecutive elements; lane
 // (g = lane / 16, e4 = lane % 16) sums copies g, g + 4, g + 8, ... of elements 4 e4 .. 4 e4 + 3 with
-// 16-B loads (each copy's 64 elements are one 256-B line; up to eight loads in flight per lane), the
-// four copy groups combine in a fixed order ((g0 + g1) + (g2 + g3)) -- deterministic -- and lane
-// (g, e4) updates element 4 e4 + g.  The split-K copies of one network are 8-32 x its size, so this
-// kernel is bound by how many of their loads are in flight (2048 x 256 threads vs one element per
-// thread and a dependent batch chain in adam_sum_kernel)
-// the four-group copy sum of adam_sum4_kernel / sum_partials4_kernel (one order for both, so a
-// world > 1 update -- sum, all-reduce, Adam on the sum x 1 / world -- is bit-equal to one rank's fused
-// step on identical data when world is a power of two)
+// 16-B loads (each copy's 64 elements are one 256-B line; up to eight loads in flight per lane), two
+// xor shuffles combine the groups, and lane (g, e4) updates element 4 e4 + g.  The split-K copies of one
+// network are 8-32 x its size, so this kernel is bound by how many of their loads are in flight.
+//
 // the eight loads of copies s0, s0 + 4, .. s0 + 28 (clamped copy index, unconditional: selected when
 // they are summed -- a select around each load would make the compiler branch and drain per load)
 __device__ __forceinline__ void copy_load8(const float *__restrict__ gpart, int ns, int64_t gs, int64_t ii, int s0,
@@ -925,21 +899,15 @@ __device__ __forceinline__ void adam4_body(const Adam4 &P, int64_t blk, int64_t 
     copy_load8(P.gpart, P.ns, P.gs, ic, g, x);
     float step_size, bc2s;
     adam_bias_bcast(bc, P.lr, P.b1, P.b2, t, step_size, bc2s);
-    const float w1 = (float)(1.0 - (double)P.b1), w2 = (float)(1.0 - (double)P.b2);
-    const float b2 = P.b2, eps = P.eps;
     while (base < P.n) {
         const f4 acc = copy_sum4(P.gpart, P.ns, P.gs, ic, g, x);
         if (k < P.n) {
             const float gi = g == 0 ? acc.x : (g == 1 ? acc.y : (g == 2 ? acc.z : acc.w));
             if (P.gout) P.gout[k] = gi;
-            float mi = m0;
-            mi = mi + w1 * (gi - mi);
-            float vi = v0 * b2;
-            vi = vi + w2 * (gi * gi);
-            const float den = sqrtf(vi) / bc2s + eps;
-            P.p[k] = p0 + (-step_size) * (mi / den);
-            P.m[k] = mi;
-            P.v[k] = vi;
+            adam_elem(p0, m0, v0, gi, P.b1, P.b2, P.eps, step_size, bc2s);
+            P.p[k] = p0;
+            P.m[k] = m0;
+            P.v[k] = v0;
         }
         base += nwaves * 64;
         if (base >= P.n) break;
@@ -978,7 +946,7 @@ __global__ void __launch_bounds__(256) sum_partials4_kernel(float *out, const fl
 
 __global__ void sum_partials_kernel(float *out, const float *__restrict__ gpart, int ns, int64_t gs, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        out[i] = sum_copies(gpart, ns, gs, i);
+        out[i] = copy_sum_seq(gpart, ns, gs, i, gpart[i]);
 }
 
 // ------------------------------------------------------------------------------ critic head
@@ -2718,6 +2686,10 @@ static int grid_for(int64_t n) {
 // both entry points pick by the same rule, so their sums are the same bits
 static bool use_sum4(const float *gpart, int ns, int64_t gstride) {
     return g_adam4 && gstride % 4 == 0 && aligned16(gpart) && ns > 1;
+}
+
+int32_t aac_copy_sum_order(const float *gpart, int32_t nsplit, int64_t gstride) {
+    return use_sum4(gpart, nsplit, gstride) ? 1 : 0;
 }
 
 static int sum4_grid(int64_t n) { return (int)std::min<int64_t>(((n + 63) / 64 + 3) / 4, 8192); }

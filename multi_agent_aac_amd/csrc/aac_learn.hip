@@ -324,17 +324,11 @@ __global__ void adam_kernel(float *p, const float *g, float *m, float *v, int64_
     float g0 = g[ic], m0 = m[ic], v0 = v[ic], p0 = p[ic];
     float step_size, bc2s;
     adam_bias_bcast(bc, lr, b1, b2, t, step_size, bc2s);
-    const float w1 = (float)(1.0 - (double)b1), w2 = (float)(1.0 - (double)b2);
     while (i < n) {
-        const float gi = g0 * gscale;
-        float mi = m0;
-        mi = mi + w1 * (gi - mi);               // exp_avg.lerp_(grad, 1 - beta1)
-        float vi = v0 * b2;                     // exp_avg_sq.mul_(beta2)
-        vi = vi + w2 * (gi * gi);               //   .addcmul_(grad, grad, 1 - beta2)
-        const float den = sqrtf(vi) / bc2s + eps;
-        p[i] = p0 + (-step_size) * (mi / den);     // param.addcdiv_(exp_avg, denom, -step_size)
-        m[i] = mi;
-        v[i] = vi;
+        adam_elem(p0, m0, v0, g0 * gscale, b1, b2, eps, step_size, bc2s);
+        p[i] = p0;
+        m[i] = m0;
+        v[i] = v0;
         i += stride;
         if (i >= n) break;
         g0 = g[i], m0 = m[i], v0 = v[i], p0 = p[i];

@@ -7,8 +7,9 @@
 //                        gradient's address to a 16-byte boundary; workgroup w takes a contiguous run
 //                        of units, thread t every 256th of them.  A unit is one 16-byte load per copy
 //                        where the copies (and the parameters) are aligned alike, scalar loads
-//                        otherwise and in the tail.  The copies are summed in the element type in the
-//                        order the Adam kernels use, then everything accumulates in double per thread
+//                        otherwise and in the tail.  The copies are summed in the element type by
+//                        sum_unit (aac_copysum.h, where the Adam kernels' sums live too), then
+//                        everything accumulates in double per thread
 //                        and folds over a fixed tree (wave butterflies, then the waves in order) into the workgroup's own slot.
 // monitor_rows_kernel    one workgroup of 16 waves per column: thread t walks rows t, t + 1024, ... of the
 //                        column's row fields, a fixed butterfly folds each wave and then the 16 wave
@@ -22,6 +23,7 @@
 #include <cmath>
 #include <string>
 
+#include "aac_copysum.h"
 #include "aac_env.h"
 #include "aac_monitor.h"
 
@@ -62,72 +64,10 @@ struct Acc {
     }
 };
 
-// V consecutive elements at p (cnt of them exist): one 16-byte load where allowed
-template <typename T, int V>
-__device__ __forceinline__ void load_unit(const T *__restrict__ p, bool wide, int cnt, T (&x)[V]) {
-    typedef T VT __attribute__((ext_vector_type(V)));
-    if (wide) {
-        const VT q = *reinterpret_cast<const VT *>(p);
-#pragma unroll
-        for (int c = 0; c < V; ++c) x[c] = q[c];
-    } else {
-#pragma unroll
-        for (int c = 0; c < V; ++c) x[c] = c < cnt ? p[c] : T(0);
-    }
-}
-
-// the summed gradient of V consecutive elements, in the element type and the Adam kernels' order
-template <typename T, int V>
-__device__ __forceinline__ void sum_unit(const T *__restrict__ g, int ns, int64_t gs, int order, bool wide, int cnt,
-                                         T (&out)[V]) {
-    T x[4][V];
-    if (order == 0) {
-        // copies 0, 1, 2, ... in sequence (four loads in flight per step)
-        load_unit<T, V>(g, wide, cnt, out);
-        int s = 1;
-        for (; s + 4 <= ns; s += 4) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) load_unit<T, V>(g + (int64_t)(s + u) * gs, wide, cnt, x[u]);
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int c = 0; c < V; ++c) out[c] += x[u][c];
-        }
-        for (; s < ns; ++s) {
-            load_unit<T, V>(g + (int64_t)s * gs, wide, cnt, x[0]);
-#pragma unroll
-            for (int c = 0; c < V; ++c) out[c] += x[0][c];
-        }
-        return;
-    }
-    // the four copy groups s % 4, each in sequence from zero, then (g0 + g1) + (g2 + g3)
-    T a[4][V];
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int c = 0; c < V; ++c) a[u][c] = T(0);
-    int s = 0;
-    for (; s + 4 <= ns; s += 4) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) load_unit<T, V>(g + (int64_t)(s + u) * gs, wide, cnt, x[u]);
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-            for (int c = 0; c < V; ++c) a[u][c] += x[u][c];
-    }
-#pragma unroll
-    for (int u = 0; u < 3; ++u) {
-        if (s + u < ns) {
-            load_unit<T, V>(g + (int64_t)(s + u) * gs, wide, cnt, x[u]);
-#pragma unroll
-            for (int c = 0; c < V; ++c) a[u][c] += x[u][c];
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < V; ++c) out[c] = (a[0][c] + a[1][c]) + (a[2][c] + a[3][c]);
-}
-
-__device__ __forceinline__ unsigned addr16(const void *p) { return (unsigned)((uintptr_t)p & 15u); }
+using aaccs::addr16;
+using aaccs::load_unit;
+using aaccs::wave_sum;
+constexpr int DEPTH = 4;      // copy loads in flight per step of a unit's sum
 
 template <typename T>
 __global__ __launch_bounds__(NT) void monitor_vec_kernel(VecArgs A) {
@@ -136,14 +76,13 @@ __global__ __launch_bounds__(NT) void monitor_vec_kernel(VecArgs A) {
     const bool second = (int)blockIdx.x >= A.first;
     const int blk = second ? (int)blockIdx.x - A.first : (int)blockIdx.x;
     const int seg = blk / WG, w = blk % WG, t = threadIdx.x;
-    const T *gbase = (const T *)(second ? A.j1.g : A.j0.g), *pbase = (const T *)(second ? A.j1.param : A.j0.param);
-    const int64_t n = second ? A.j1.n : A.j0.n, gs = second ? A.j1.gstride : A.j0.gstride;
-    const int64_t sstride = second ? A.j1.seg_stride : A.j0.seg_stride;
-    const int ns = second ? A.j1.nsplit : A.j0.nsplit, order = second ? A.j1.order : A.j0.order;
-    const int col = (second ? A.j1.col0 : A.j0.col0) + seg, net = second ? A.j1.net : A.j0.net;
-    const T gscale = (T)(second ? A.j1.gscale : A.j0.gscale);
-    double *scratch = second ? A.j1.scratch : A.j0.scratch;
-    const T *__restrict__ g = gbase + seg * sstride, *__restrict__ p = pbase + seg * sstride;
+    const aac_monitor_vec_job &j = second ? A.j1 : A.j0;
+    const int64_t n = j.n, gs = j.gstride, sstride = j.seg_stride;
+    const int ns = j.nsplit, order = j.order;
+    const int col = j.col0 + seg, net = j.net;
+    const T gscale = (T)j.gscale;
+    double *scratch = j.scratch;
+    const T *__restrict__ g = (const T *)j.g + seg * sstride, *__restrict__ p = (const T *)j.param + seg * sstride;
     // 16-byte loads of the gradient need every copy aligned alike; the head is counted from the
     // gradient then, else from the parameters
     const bool gcopies = ns == 1 || (gs * (int64_t)sizeof(T)) % 16 == 0;
@@ -153,7 +92,7 @@ __global__ __launch_bounds__(NT) void monitor_vec_kernel(VecArgs A) {
     Acc ag, ap;
     if (w == 0 && t < h) {      // the scalar head
         T x[V], y[V];
-        sum_unit<T, V>(g + t, ns, gs, order, false, 1, x);
+        aaccs::sum_unit<T, V, DEPTH>(g + t, ns, gs, order, false, 1, x);
         load_unit<T, V>(p + t, false, 1, y);
         ag.add((double)(x[0] * gscale));
         ap.add((double)y[0]);
@@ -165,7 +104,7 @@ __global__ __launch_bounds__(NT) void monitor_vec_kernel(VecArgs A) {
         const int cnt = n - i0 < V ? (int)(n - i0) : V;
         const bool full = cnt == V;
         T x[V], y[V];
-        sum_unit<T, V>(g + i0, ns, gs, order, wide_g && full, cnt, x);
+        aaccs::sum_unit<T, V, DEPTH>(g + i0, ns, gs, order, wide_g && full, cnt, x);
         load_unit<T, V>(p + i0, wide_p && full, cnt, y);
 #pragma unroll
         for (int c = 0; c < V; ++c) {
@@ -197,11 +136,6 @@ __global__ __launch_bounds__(NT) void monitor_vec_kernel(VecArgs A) {
     }
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 __device__ __forceinline__ double wave_max(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));

@@ -21,6 +21,7 @@
 
 #include "../../include/aac_uam_learn.h"
 #include "aac_adam_bc.h"
+#include "aac_copysum.h"
 
 namespace {
 
@@ -274,22 +275,12 @@ __global__ void adam64_kernel(double *p, const double *__restrict__ gpart, int n
     double step_size, bc2s;
     adam_bias_bcast(bc, lr, b1, b2, t, step_size, bc2s);
     while (i < n) {
-        int s = 1;
-        for (; s + 8 <= ns; s += 8) {
-            double x[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) x[u] = gpart[(int64_t)(s + u) * n + i];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) gi += x[u];
-        }
-        for (; s < ns; ++s) gi += gpart[(int64_t)s * n + i];
+        gi = aaccs::copy_sum_seq(gpart, ns, n, i, gi);
         gi *= gscale;           // 1 / world after a SUM all-reduce (1 otherwise); the mean exactly for power-of-two worlds
-        const double mi = b1 * m0 + (1.0 - b1) * gi;
-        const double vi = b2 * v0 + (1.0 - b2) * gi * gi;
-        const double den = sqrt(vi) / bc2s + eps;
-        p[i] = p0 - step_size * mi / den;
-        m[i] = mi;
-        v[i] = vi;
+        adam_elem(p0, m0, v0, gi, b1, b2, eps, step_size, bc2s);
+        p[i] = p0;
+        m[i] = m0;
+        v[i] = v0;
         i += stride;
         if (i >= n) break;
         gi = gpart[i], m0 = m[i], v0 = v[i], p0 = p[i];
@@ -299,19 +290,8 @@ __global__ void adam64_kernel(double *p, const double *__restrict__ gpart, int n
 // the fixed-order sum of ns partial copies (the adam64_kernel order): the gradient a multi-rank
 // update all-reduces before its Adam step (aac_adam64_sum with nsplit = 1 on the result)
 __global__ void sum64_kernel(double *out, const double *__restrict__ gpart, int ns, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        double gi = gpart[i];
-        int s = 1;
-        for (; s + 8 <= ns; s += 8) {
-            double x[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) x[u] = gpart[(int64_t)(s + u) * n + i];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) gi += x[u];
-        }
-        for (; s < ns; ++s) gi += gpart[(int64_t)s * n + i];
-        out[i] = gi;
-    }
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        out[i] = aaccs::copy_sum_seq(gpart, ns, n, i, gpart[i]);
 }
 
 __global__ void uam_polyak_kernel(double *tgt, const double *__restrict__ src, int64_t n, double tau, int32_t *step,

@@ -89,6 +89,8 @@ def lib():
         L.aac_adam_flat_sum.argtypes = [vp, vp, i32, vp, vp, vp, i64, f32, f32, f32, f32, vp, i32, vp]
         L.aac_sum_partials.argtypes = [vp, vp, i32, i64, vp]
         L.aac_sum_partials_strided.argtypes = [vp, vp, i32, i64, i64, vp]
+        L.aac_copy_sum_order.argtypes = [vp, i32, i64]
+        L.aac_copy_sum_order.restype = i32
         L.aac_adam_flat_sum_pair.argtypes = [ctypes.POINTER(AdamJob), ctypes.POINTER(AdamJob), vp]
         L.aac_adam_flat_sum_strided.argtypes = [vp, vp, i32, i64, vp, vp, vp, i64, f32, f32, f32, f32, vp, i32, vp]
         L.aac_critic_head.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, i32, i32, f32, vp, vp, vp, vp, vp]
@@ -377,10 +379,9 @@ def _adam_job(opt, gpart, nsplit, step_add, grad_out):
 
 
 def adam_pair_ok(*gparts):
-    """aac_adam_flat_sum_pair's conditions: the copy-parallel Adam (AAC_ADAM4) over >= 2 copies at
-    a 16-B aligned stride."""
-    return os.environ.get("AAC_ADAM4", "1") != "0" and all(
-        g.shape[0] >= 2 and g.shape[-1] % 4 == 0 and g.data_ptr() % 16 == 0 for g in gparts)
+    """aac_adam_flat_sum_pair's conditions: the copy-parallel Adam (``adam4_order`` 1) for every set of
+    copies ([nsplit][stride])."""
+    return all(adam4_order(g, g.shape[0]) == 1 for g in gparts)
 
 
 def adam_sum_pair(a, b):
@@ -392,6 +393,13 @@ def adam_sum_pair(a, b):
 def sum_partials(out, gpart, nsplit):
     _chk(lib().aac_sum_partials_strided(vp(out.data_ptr()), vp(gpart.data_ptr()), nsplit, gpart.shape[-1],
                                         out.numel(), _stream()), "aac_sum_partials")
+
+
+def adam4_order(gpart, nsplit):
+    """The copy order ``adam_sum`` / ``sum_partials`` take for these partial copies (aac_copy_sum_order):
+    1 = the four-group copy-parallel sum, 0 = the copies in sequence.  The ``order`` of a clip or
+    monitor job that must reproduce their sum."""
+    return lib().aac_copy_sum_order(vp(gpart.data_ptr()), nsplit, gpart.shape[-1])
 
 
 def padded(n, q=4):
@@ -796,7 +804,6 @@ class FusedUpdate:
             return None
         if m.world > 1:
             return self.clip.step(net, opt, flat.grad, step_add=step_add, gscale=1.0 / m.world)
-        from .monitor import adam4_order
         return self.clip.step(net, opt, gpart, nsplit=ns, gstride=gpart.shape[-1], order=adam4_order(gpart, ns),
                               grad_out=flat.grad, step_add=step_add)
 
@@ -838,7 +845,6 @@ class FusedUpdate:
         summed, in its order) and of the parameters it just wrote.  [] without a monitor."""
         if self.mon is None:
             return []
-        from .monitor import adam4_order
         m, jobs = self.m, []
         for col, net, gpart, ns, flat in ((i_critic, 0, self.gc, self.SPLIT_CRITIC, m.fc),
                                           (i_actor, 1, self.ga, self.SPLIT_ACTOR, m.fa)):

@@ -16,12 +16,12 @@ the reference's names (ATT/main:575-580, ATT/maddpg:372-379, :442-453):
 """
 import ctypes
 import math
-import os
 
 import numpy as np
 import torch
 
 from . import _native
+from .fused import adam4_order  # noqa: F401  (the order field of a vec job that follows adam_sum / sum_partials)
 
 FIELDS = 27           # AAC_MONITOR_FIELDS
 VEC_WG = 64           # AAC_MONITOR_VEC_WG
@@ -201,12 +201,4 @@ class LearnerMonitor:
         bad = self.bad_update()
         if bad >= 0:
             raise FloatingPointError(f"learner monitor: non-finite values first seen in update {bad}")
-
-
-def adam4_order(gpart, nsplit):
-    """The float Adam / partial-sum kernels' copy order for these partial copies: 1 = the four-group
-    copy-parallel sum (16-byte aligned copies at a stride that is a multiple of 4, AAC_ADAM4 on), 0 =
-    the copies in sequence."""
-    return int(os.environ.get("AAC_ADAM4", "1") != "0" and nsplit > 1 and gpart.shape[-1] % 4 == 0
-               and gpart.data_ptr() % 16 == 0)
 
