@@ -28,6 +28,7 @@ EXPORTS = (
     "aac_env_probe",
     "aac_env_reward_map",
     "aac_uam_reward_map",
+    "aac_uam_probe",
 )
 
 vp = ctypes.c_void_p
@@ -128,6 +129,10 @@ class ProbeOut(ctypes.Structure):          # aac_probe_out (include/aac_probe.h)
     _fields_ = [(n, vp) for n in ("dist", "point", "end", "kind", "id")]
 
 
+class UamProbeOut(ctypes.Structure):       # aac_uam_probe_out (include/aac_uam_probe.h)
+    _fields_ = [(n, vp) for n in ("dist", "point", "end", "kind", "id")]
+
+
 class RmapOut(ctypes.Structure):           # aac_rmap_out (include/aac_rmap.h)
     _fields_ = [(n, vp) for n in ("reward", "terms", "mask", "done", "bbc")]
 
@@ -200,6 +205,8 @@ def lib():
         L.aac_env_reward_map.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_int64, ctypes.POINTER(RmapOut), vp]
     if hasattr(L, "aac_uam_reward_map") or not os.environ.get("AAC_LIB"):
         L.aac_uam_reward_map.argtypes = [vp, vp, vp, vp, vp, vp, vp, ctypes.c_int64, ctypes.POINTER(UamRmapOut), vp]
+    if hasattr(L, "aac_uam_probe") or not os.environ.get("AAC_LIB"):
+        L.aac_uam_probe.argtypes = [vp, vp, vp, vp, ctypes.c_int64, vp, ctypes.POINTER(UamProbeOut), vp]
     for name in EXPORTS:
         if os.environ.get("AAC_LIB") and not hasattr(L, name):
             continue          # an A/B experiment build of an earlier revision

@@ -26,6 +26,7 @@
 #include "../../include/aac_uam.h"
 #include "../../include/aac_terms.h"
 #include "../../include/aac_uam_rmap.h"
+#include "../../include/aac_uam_probe.h"
 #include "aac_geom.h"
 #include "aac_wave.h"
 
@@ -1217,6 +1218,138 @@ __global__ void __launch_bounds__(BLOCK) uam_reward_map_kernel(UArgs A, UMap Q) 
     }
 }
 
+// Radar probes (include/aac_uam_probe.h; UAM/env:1346-1495): the map's radar section with the winning
+// candidate kept beside the minimum.  Work mapping as the reward map's: a 256-thread workgroup takes
+// PROBE_PAIRS = 14 (row, aircraft) pairs; thread t < 14 * 18 is the work item (pair t / 18, ray t % 18) and
+// walks that ray's candidates itself, the other aircraft's positions from global memory.  No LDS, no barrier,
+// no cross-lane operation, no atomics: every record is written by the one work item that formed it.
+#define PROBE_PAIRS AAC_UAM_PROBE_PAIRS
+
+struct UProbe {
+    int64_t M;
+    const double2 *pos, *clouds;      // given rows, or null: the handle's live state
+    const int32_t *env_idx;
+    const uint8_t *sel;
+    double *dist;
+    double2 *point, *end;
+    uint8_t *kind;
+    int32_t *id;
+};
+
+// ray_vseg / ray_hseg with the crossing's point: the same tests and expression order
+__device__ inline bool ray_vseg_pt(double cx, double cy, double ex, double ey, double lx, double y0, double y1, double &d,
+                                   double &hx, double &hy) {
+    if ((cx - lx) * (ex - lx) > 0.0 || ex == cx) return false;
+    const double t = (lx - cx) / (ex - cx);
+    const double y = cy + t * (ey - cy);
+    if (y < y0 || y > y1) return false;
+    hx = lx;
+    hy = y;
+    d = gdist(lx, y, cx, cy);
+    return true;
+}
+
+__device__ inline bool ray_hseg_pt(double cx, double cy, double ex, double ey, double ly, double x0, double x1, double &d,
+                                   double &hx, double &hy) {
+    if ((cy - ly) * (ey - ly) > 0.0 || ey == cy) return false;
+    const double t = (ly - cy) / (ey - cy);
+    const double x = cx + t * (ex - cx);
+    if (x < x0 || x > x1) return false;
+    hx = x;
+    hy = ly;
+    d = gdist(x, ly, cx, cy);
+    return true;
+}
+
+// ray_clip_dist_at with the clip's point
+__device__ inline double ray_clip_pt_at(double cx, double cy, double ex, double ey, double inv_l2, double qx, double qy,
+                                        double rad, bool &hit, double &hx, double &hy) {
+    double t;
+    hit = ray_gon_candidate(cx, cy, ex, ey, qx, qy, rad, inv_l2) &&
+          ray_gon_boundary_cand(cx, cy, ex, ey, qx, qy, rad, t);
+    if (!hit) return 0.0;
+    hx = cx + t * (ex - cx);
+    hy = cy + t * (ey - cy);
+    return gdist(hx, hy, cx, cy);
+}
+
+__global__ void __launch_bounds__(BLOCK) uam_probe_kernel(UArgs A, UProbe Q) {
+    const int N = A.N;
+    const int t = threadIdx.x;
+    const int lp = t / NRAY, r = t - lp * NRAY;
+    const int64_t pr = (int64_t)blockIdx.x * PROBE_PAIRS + lp;
+    if (lp >= PROBE_PAIRS || pr >= Q.M * N) return;
+    const int64_t m = pr / N;
+    const int i = (int)(pr - m * N);
+    if (Q.sel && !Q.sel[m]) return;
+    int e;
+    if (Q.pos) {
+        e = Q.env_idx ? Q.env_idx[m] : (int)(m % A.E);
+        e = e < 0 ? 0 : (e >= A.E ? A.E - 1 : e);
+    } else {
+        e = (int)m;                     // the host has M == E
+    }
+    const double2 *row = Q.pos ? Q.pos + m * N : A.pos + (size_t)e * N;
+    const double2 *cl = Q.clouds ? Q.clouds + m * 2 : A.clouds + (size_t)e * 2;
+    const double2 p = row[i];
+    const double cx = p.x, cy = p.y;
+    const double ex = cx + A.radar_len * c_tab.ray_c[r], ey = cy + A.radar_len * c_tab.ray_s[r];
+    double best = gdist(ex, ey, cx, cy);
+    double bx = ex, by = ey;
+    int kind = AAC_UAM_PROBE_NONE, id = -1;
+    double d, hx, hy;
+    const double *rw = c_world.runway;
+    bool band = false;
+    if (fmax(cx, ex) >= rw[0] - 1e-9 && fmin(cx, ex) <= rw[1] + 1e-9 && fmax(cy, ey) >= rw[2] - 1e-9 &&
+        fmin(cy, ey) <= rw[3] + 1e-9 && ray_square_pt<0>(cx, cy, ex, ey, rw[0], rw[1], rw[2], rw[3], d, hx, hy, band) &&
+        d < best) {
+        best = d, bx = hx, by = hy;
+        kind = AAC_UAM_PROBE_RUNWAY, id = 0;
+    }
+    const double *b = A.bound;
+    if (ray_vseg_pt(cx, cy, ex, ey, b[0], b[2], b[3], d, hx, hy) && d < best) {
+        best = d, bx = hx, by = hy;
+        kind = AAC_UAM_PROBE_BOUND, id = 0;
+    }
+    if (ray_vseg_pt(cx, cy, ex, ey, b[1], b[2], b[3], d, hx, hy) && d < best) {
+        best = d, bx = hx, by = hy;
+        kind = AAC_UAM_PROBE_BOUND, id = 1;
+    }
+    if (ray_hseg_pt(cx, cy, ex, ey, b[3], b[0], b[1], d, hx, hy) && d < best) {
+        best = d, bx = hx, by = hy;
+        kind = AAC_UAM_PROBE_BOUND, id = 2;
+    }
+    if (ray_hseg_pt(cx, cy, ex, ey, b[2], b[0], b[1], d, hx, hy) && d < best) {
+        best = d, bx = hx, by = hy;
+        kind = AAC_UAM_PROBE_BOUND, id = 3;
+    }
+    const double inv_l2 = 1.0 / ((ex - cx) * (ex - cx) + (ey - cy) * (ey - cy));
+    bool hit;
+    for (int k = 0; k < 2; ++k) {
+        const double2 c = cl[k];
+        d = ray_clip_pt_at(cx, cy, ex, ey, inv_l2, c.x, c.y, c_world.radius[k], hit, hx, hy);
+        if (hit && d < best) {
+            best = d, bx = hx, by = hy;
+            kind = AAC_UAM_PROBE_CLOUD, id = k;
+        }
+    }
+    for (int j = 0; j < N; ++j) {
+        if (j == i) continue;
+        const double2 q = row[j];
+        d = ray_clip_pt_at(cx, cy, ex, ey, inv_l2, q.x, q.y, A.pb, hit, hx, hy);
+        if (hit && d < best) {
+            best = d, bx = hx, by = hy;
+            kind = AAC_UAM_PROBE_AIRCRAFT, id = j;
+        }
+    }
+    const int64_t o = pr * NRAY + r;
+    Q.dist[o] = best;
+    Q.point[o] = make_double2(bx, by);
+    if (Q.end) Q.end[o] = make_double2(ex, ey);
+    Q.kind[o] = (uint8_t)kind;
+    Q.id[o] = id;
+}
+
 // exactness check of ray_gon_boundary's fast paths against the full clip (aac_uam_ray_gon_check):
 // random segments of radar length from points around a 64-gon, focused on the inside / annulus /
 // near-tangent cases; counts results that differ in the hit flag or any bit of t
@@ -1614,6 +1747,39 @@ int aac_uam_reward_map(aac_uam *h, const double *points, const double *pre, cons
     Q.bbc = out->bbc;
     Q.flags = out->flags;
     hipLaunchKernelGGL(uam_reward_map_kernel, dim3((unsigned)blocks), dim3(BLOCK), 0, (hipStream_t)stream, A, Q);
+    UCHK(hipGetLastError());
+    return AAC_OK;
+}
+
+int aac_uam_probe(aac_uam *h, const double *pos, const double *clouds, const int32_t *env_idx, int64_t M,
+                  const uint8_t *sel, const aac_uam_probe_out *out, void *stream) {
+    if (!h || !out) return ufail(AAC_E_INVALID, "uam_probe: null handle or out");
+    if (!out->dist || !out->point || !out->kind || !out->id)
+        return ufail(AAC_E_INVALID, "uam_probe: dist, point, kind, id required");
+    if ((reinterpret_cast<uintptr_t>(pos) | reinterpret_cast<uintptr_t>(clouds) | reinterpret_cast<uintptr_t>(out->point) |
+         reinterpret_cast<uintptr_t>(out->end)) & 15)
+        return ufail(AAC_E_INVALID, "uam_probe: pos, clouds, point and end must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(out->dist) & 7) || (reinterpret_cast<uintptr_t>(out->id) & 3) ||
+        (reinterpret_cast<uintptr_t>(env_idx) & 3))
+        return ufail(AAC_E_INVALID, "uam_probe: dist must be 8-byte, id and env_idx 4-byte aligned");
+    if (M < 1 || M > (int64_t)1 << 40) return ufail(AAC_E_INVALID, "uam_probe: M out of range");
+    if (!pos && M != h->cfg.E) return ufail(AAC_E_INVALID, "uam_probe: the live state has E rows");
+    const int64_t blocks = (M * h->cfg.N + PROBE_PAIRS - 1) / PROBE_PAIRS;
+    if (blocks > 0x7fffffff) return ufail(AAC_E_INVALID, "uam_probe: M out of range");
+    const aac_uam_out none{};
+    const UArgs A = make_uargs(h, &none);
+    UProbe Q;
+    Q.M = M;
+    Q.pos = reinterpret_cast<const double2 *>(pos);
+    Q.clouds = reinterpret_cast<const double2 *>(clouds);
+    Q.env_idx = env_idx;
+    Q.sel = sel;
+    Q.dist = out->dist;
+    Q.point = reinterpret_cast<double2 *>(out->point);
+    Q.end = reinterpret_cast<double2 *>(out->end);
+    Q.kind = out->kind;
+    Q.id = out->id;
+    hipLaunchKernelGGL(uam_probe_kernel, dim3((unsigned)blocks), dim3(BLOCK), 0, (hipStream_t)stream, A, Q);
     UCHK(hipGetLastError());
     return AAC_OK;
 }

@@ -27,7 +27,7 @@ BOUND = (0.0, 40.0, 0.0, 40.0)               # UAM/params:32-36
 EXPORTS = ("aac_uam_create", "aac_uam_destroy", "aac_uam_last_error", "aac_uam_reset", "aac_uam_step",
            "aac_uam_set_bank", "aac_uam_auto_reset", "aac_uam_bank_build", "aac_uam_get_state",
            "aac_uam_set_state", "aac_uam_actor", "aac_uam_actor_last_error", "aac_uam_set_reset_compact",
-           "aac_uam_use_episode_buffer", "aac_uam_set_terms_buffer", "aac_uam_reward_map")
+           "aac_uam_use_episode_buffer", "aac_uam_set_terms_buffer", "aac_uam_reward_map", "aac_uam_probe")
 
 
 class UamCfg(ctypes.Structure):
@@ -275,6 +275,7 @@ class BatchedUAM:
 GO_AC = ((20, 20, 20, 35, 5, 35, 5, 5, 20, 5, 20, 20), (20, 20, 20, 5, 5, 5, 5, 35, 20, 35, 20, 20),
          (20, 20, 20, 35, 35, 35, 35, 5, 20, 5, 20, 20), (20, 20, 20, 5, 35, 5, 35, 35, 20, 35, 20, 20))
 CLOUDS = ((8, 30, 10, 10), (30, 10, 35, 30))
+RUNWAY = (18.0, 22.0, 10.0, 30.0)            # x0, x1, y0, y1 (UAM/env:559)
 
 
 class Agent:
@@ -323,10 +324,21 @@ class env_simulator:
     ``ss_reward_Mar_changeskin`` fills ``eps_status_holder[i]`` with the per-step pieces the reference hands
     its loop (UAM/env:4651-4665) that the kernel supplies, penalties unsigned as there:
     ``goal_leading_reward``, ``near_building_penalty``, ``near_drone_penalty``, ``current_drone_speed``,
-    ``Euclidean_dist_to_goal``, and ``deviation_to_ref_line`` (the cross-track gauge, an extra key)."""
+    ``Euclidean_dist_to_goal``, and ``deviation_to_ref_line`` (the cross-track gauge, an extra key).
+
+    ``radar_probes=True`` runs a radar probe (``probe.UamRadarProbe``, include/aac_uam_probe.h) after every
+    ``step`` and ``reset_world_change_skin``; ``last_probes`` holds its full ``read()`` dict, and ``step``
+    returns the reference's six lists beside the state (UAM/env:1316-1320, :1346-1495, :4904), as tuples and
+    numpy, no shapely objects: ``polygons_list`` (the runway, a (4, 2) array of the corners (x0, y0),
+    (x0, y1), (x1, y1), (x1, y0)), ``all_agent_st_points`` (per aircraft ``{deg: centre}``),
+    ``all_agent_ed_points`` (per aircraft ``{deg: point}``: the nearest intersection, or the ray end when
+    nothing is hit -- this variant overwrites the end point), ``all_agent_intersection_point_list`` and
+    ``all_agent_mini_intersection_list`` (one empty list per aircraft: this variant never appends to them)
+    and ``all_agent_line_collection`` (per aircraft the 18 ``((sx, sy), (ex, ey))`` segments, centre to ray
+    end).  Off (the default): six empty lists."""
 
     def __init__(self, world_map=None, building_polygons=None, grid_length=1, bound=None, allGridPoly=None,
-                 agentConfig=None, seed=None, reward_terms=False):
+                 agentConfig=None, seed=None, reward_terms=False, radar_probes=False):
         self.world_map_2D = world_map
         self.buildingPolygons = building_polygons
         self.world_map_2D_polyList = allGridPoly
@@ -341,6 +353,9 @@ class env_simulator:
         self._draws = 0
         self._env = None
         self.reward_terms = bool(reward_terms)
+        self.radar_probes = bool(radar_probes)
+        self.last_probes = None
+        self._probe = None
 
     def create_world(self, total_agentNum, n_actions, gamma, tau, target_update, largest_Nsigma, smallest_Nsigma,
                      ini_Nsigma, max_xy, max_spd, acc_range):
@@ -355,6 +370,9 @@ class env_simulator:
                                bound=self.bound, p3=True)
         if self.reward_terms:
             self._env.use_terms_buffer()
+        if self.radar_probes:
+            from .probe import UamRadarProbe
+            self._probe = UamRadarProbe.for_uam(self._env)
 
     def reset_world_change_skin(self, total_agentNum, full_observable_critic_flag=False, evaluation_by_fixed_ar=False,
                                 include_other_AC=True, use_nearestN_neigh_wRadar=False, N_neigh=2, args=None,
@@ -381,7 +399,25 @@ class env_simulator:
             ag.removed_goal = None
             ag.bound_collision = ag.building_collision = ag.cloud_collision = ag.drone_collision = False
         self._sync()
+        if self._probe is not None:
+            self._probe.run()
+            self.last_probes = self._probe.read()
         return self._states()
+
+    def _probe_lists(self):
+        """The reference's six lists of the step (class docstring) from a probe of the live state."""
+        self._probe.run()
+        pr = self.last_probes = self._probe.read()
+        x0, x1, y0, y1 = RUNWAY
+        st, ed, lines = [], [], []
+        for i, ag in self.all_agents.items():
+            c = (float(ag.pos[0]), float(ag.pos[1]))
+            st.append({20 * r: c for r in range(N_RAYS)})
+            ed.append({20 * r: (float(pr["point"][0, i, r, 0]), float(pr["point"][0, i, r, 1])) for r in range(N_RAYS)})
+            lines.append([(c, (float(x), float(y))) for x, y in pr["end"][0, i]])
+        n = len(self.all_agents)
+        return ([np.array([(x0, y0), (x0, y1), (x1, y1), (x1, y0)])], st, ed, [[] for _ in range(n)], lines,
+                [[] for _ in range(n)])
 
     def _sync(self):
         s = {k: v.cpu().numpy() for k, v in self._env.get_state().items()}
@@ -438,7 +474,9 @@ class env_simulator:
             self._last["terms"] = self._env.terms[0].cpu().numpy()
         self._sync()
         state, norm = self._states()
-        return state, norm, [], [], [], [], [], []
+        if self._probe is None:
+            return state, norm, [], [], [], [], [], []
+        return (state, norm) + self._probe_lists()
 
     def ss_reward_Mar_changeskin(self, current_ts, step_reward_record, step_collision_record, xy=(None, None),
                                  full_observable_critic_flag=False, args=None, evaluation_by_episode=True,
