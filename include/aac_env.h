@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "aac_record.h"
+#include "aac_visits.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -164,6 +165,13 @@ int aac_env_set_terms_buffer(aac_env *env, double *terms_dev);
  * aac_env_reset / aac_env_auto_reset, STEP after aac_env_step and before any reset; state->N must be
  * the handle's N.  One launch on ``stream``, capturable. */
 int aac_env_record(aac_env *env, const aac_record_state *state, const aac_record_step *step, void *stream);
+
+/* Exploration maps (aac_visits.h): aac_visits_accumulate with E, N and the state sources of ``step``
+ * (pos, map_idx and the episode counter, wherever aac_env_use_episode_buffer has put it) filled from the
+ * handle's live device pointers at call time; act, sel and explore_until are the caller's.  Called
+ * between the act launch and the step launch it counts the position each action is taken from.
+ * state->n_maps must be the handle's n_maps.  One launch on ``stream``, capturable. */
+int aac_env_visits(aac_env *env, const aac_visits_state *state, const aac_visits_step *step, void *stream);
 
 /* State export / import (device pointers, each may be NULL to skip).  `start` (double2[E][N]) is
  * the episode start: the reference-path origin of the WGRU variant's cross-track reward

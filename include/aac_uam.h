@@ -94,6 +94,12 @@ int aac_uam_set_terms_buffer(aac_uam *env, double *terms_dev);
  * state->N must be the handle's N.  One launch on ``stream``, capturable. */
 int aac_uam_record(aac_uam *env, const aac_record_state *state, const aac_record_step *step, void *stream);
 
+/* Exploration maps (aac_visits.h): aac_visits_accumulate with E, N, pos and the episode counter (wherever
+ * aac_uam_use_episode_buffer has put it; no map_idx) filled from the handle's live device pointers at
+ * call time; act (double, act_f64 = 1), sel and explore_until are the caller's.  One launch on
+ * ``stream``, capturable. */
+int aac_uam_visits(aac_uam *env, const aac_visits_state *state, const aac_visits_step *step, void *stream);
+
 /* Host: draw n episodes with the reference's rules (UAM/env:575-747, UAM/util:165-237): cloud
  * choices, starts in the two start zones re-drawn until > 3 pB from earlier starts, ends uniform
  * over the no-spawn-subtracted regions on the start's side of the runway. */

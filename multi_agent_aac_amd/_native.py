@@ -29,6 +29,7 @@ EXPORTS = (
     "aac_env_reward_map",
     "aac_uam_reward_map",
     "aac_uam_probe",
+    "aac_visits_last_error", "aac_visits_accumulate", "aac_env_visits", "aac_uam_visits",
 )
 
 vp = ctypes.c_void_p
@@ -141,6 +142,17 @@ class UamRmapOut(ctypes.Structure):        # aac_uam_rmap_out (include/aac_uam_r
     _fields_ = [(n, vp) for n in ("reward", "terms", "mask", "done", "bbc", "flags", "rays")]
 
 
+class VisitsState(ctypes.Structure):       # aac_visits_state (include/aac_visits.h)
+    _fields_ = [("pos_hist", vp), ("act_hist", vp), ("counters", vp)] + \
+               [(n, i32) for n in ("GX", "GY", "A", "n_maps")] + \
+               [(n, ctypes.c_double) for n in ("x0", "x1", "y0", "y1", "a0", "a1")]
+
+
+class VisitsStep(ctypes.Structure):        # aac_visits_step
+    _fields_ = [(n, vp) for n in ("pos", "act", "episode", "map_idx", "sel")] + \
+               [(n, i32) for n in ("act_f64", "E", "N", "explore_until")]
+
+
 _lib = None
 
 
@@ -207,6 +219,12 @@ def lib():
         L.aac_uam_reward_map.argtypes = [vp, vp, vp, vp, vp, vp, vp, ctypes.c_int64, ctypes.POINTER(UamRmapOut), vp]
     if hasattr(L, "aac_uam_probe") or not os.environ.get("AAC_LIB"):
         L.aac_uam_probe.argtypes = [vp, vp, vp, vp, ctypes.c_int64, vp, ctypes.POINTER(UamProbeOut), vp]
+    if hasattr(L, "aac_visits_accumulate") or not os.environ.get("AAC_LIB"):
+        vis = [ctypes.POINTER(VisitsState), ctypes.POINTER(VisitsStep), vp]
+        L.aac_visits_last_error.restype = ctypes.c_char_p
+        L.aac_visits_accumulate.argtypes = vis
+        L.aac_env_visits.argtypes = [vp] + vis
+        L.aac_uam_visits.argtypes = [vp] + vis
     for name in EXPORTS:
         if os.environ.get("AAC_LIB") and not hasattr(L, name):
             continue          # an A/B experiment build of an earlier revision

@@ -2419,6 +2419,19 @@ int aac_env_record(aac_env *h, const aac_record_state *state, const aac_record_s
     return AAC_OK;
 }
 
+int aac_env_visits(aac_env *h, const aac_visits_state *state, const aac_visits_step *step, void *stream) {
+    if (!h || !state || !step) return fail(AAC_E_INVALID, "null argument");
+    if (state->n_maps != h->cfg.n_maps) return fail(AAC_E_INVALID, "env_visits: state->n_maps is not the handle's n_maps");
+    aac_visits_step p = *step;
+    p.E = h->cfg.E;
+    p.N = h->cfg.N;
+    p.pos = (const double *)h->pos;
+    p.episode = h->episode;
+    p.map_idx = h->map_idx;
+    if (int rc = aac_visits_accumulate(state, &p, stream)) return fail(rc, aac_visits_last_error());
+    return AAC_OK;
+}
+
 int aac_env_probe(aac_env *h, const double *pos_dev, const int32_t *map_idx_dev, int64_t M, const uint8_t *sel_dev,
                   const aac_probe_out *out, void *stream) {
     if (!h || !out) return fail(AAC_E_INVALID, "null argument");

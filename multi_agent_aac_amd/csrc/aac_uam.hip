@@ -1841,6 +1841,18 @@ int aac_uam_record(aac_uam *h, const aac_record_state *state, const aac_record_s
     return AAC_OK;
 }
 
+int aac_uam_visits(aac_uam *h, const aac_visits_state *state, const aac_visits_step *step, void *stream) {
+    if (!h || !state || !step) return ufail(AAC_E_INVALID, "null argument");
+    aac_visits_step p = *step;
+    p.E = h->cfg.E;
+    p.N = h->cfg.N;
+    p.pos = (const double *)h->pos;
+    p.episode = h->episode;
+    p.map_idx = nullptr;
+    if (int rc = aac_visits_accumulate(state, &p, stream)) return ufail(rc, aac_visits_last_error());
+    return AAC_OK;
+}
+
 #define UCPY(dst, src, n)                                                                                   \
     if (dst && src) UCHK(hipMemcpyAsync((void *)(dst), (const void *)(src), (n), hipMemcpyDeviceToDevice,   \
                                         (hipStream_t)stream));

@@ -29,9 +29,18 @@ class Evaluator:
     ``terms=True`` (ATT, GRU and UAM trainers): the eval env gets a reward-terms buffer and a reward ledger
     (``terms.RewardLedger``) fed beside the statistics under the same quota, so it holds the same
     episode set; ``evaluate`` then returns ``(stats, ledger.read())`` and ``record``
-    ``(stats, Trajectories, ledger.read())``, the trajectories with a ``terms`` array."""
+    ``(stats, Trajectories, ledger.read())``, the trajectories with a ``terms`` array.
 
-    def __init__(self, trainer, E=None, seed=0, log=0, terms=False):
+    ``visits=True`` (or a dict of ``visits.VisitMap`` keywords): ``self.visits`` keeps the exploration maps
+    of the noise-free rollout -- the positions and actions of the episodes the statistics count (an env
+    at its quota adds nothing more) -- emptied at the start of every ``evaluate`` / ``record`` call and
+    read with ``self.visits.read()``.  The eval env counts episodes of its own, so every sample of a call
+    goes into ONE period: the one the training loop is in, read at the start of the call from the
+    TRAINING env's per-env episode counter (``trainer.episode``, the counter the noise schedule reads):
+    "explore" while its minimum over the envs is ``<= explore_until``, i.e. until every training env has
+    left the noise schedule, "exploit" afterwards.  The read synchronises."""
+
+    def __init__(self, trainer, E=None, seed=0, log=0, terms=False, visits=False):
         self.tr, self.model = trainer, trainer.model
         tenv = trainer.env
         self.E, self.N = int(E or trainer.E), trainer.N
@@ -62,6 +71,13 @@ class Evaluator:
         if terms:
             from .terms import RewardLedger
             self.ledger = RewardLedger.for_uam(self.env) if self.uam else RewardLedger.for_env(self.env)
+        self.visits = self._vis_sel = None
+        self._period = None     # the period of this call's samples (None without a visit map)
+        if visits:
+            from .visits import VisitMap
+            self.visits = VisitMap(self.env, **(dict(visits) if isinstance(visits, dict) else {}))
+            self._vis_sel = torch.zeros(self.E, dtype=torch.bool, device=dev)
+            self._vis_sel_u8 = self._vis_sel.view(torch.uint8)
         if self.gru:
             from . import gru
             # hidden states as the trainer's ping-pong pair, and act plans of this object's own: the
@@ -69,7 +85,7 @@ class Evaluator:
             self.hp = [torch.zeros(self.E, self.N, gru.H, device=dev) for _ in range(2)]
             self._acts = [gru._ActPlan(self.model, self.bufs[p].own, self.bufs[p].radar, self.hp[p], self.hp[1 - p])
                           for p in range(2)]
-        self._graphs = None
+        self._graphs = {}       # period -> the pair of step graphs
         self._rec = self._rec_key = self._rec_graphs = None     # built by the first record()
 
     def _start(self):
@@ -79,6 +95,19 @@ class Evaluator:
             self.hp[0].zero_()
         self.env.auto_reset(None, out=self.bufs[0])
 
+    def _visit(self, act):
+        """The visit map's launch, after the act launch: the envs still under their quota, as the
+        statistics count them."""
+        if self.visits is not None:
+            torch.lt(self.stats.ep_count, self.quota, out=self._vis_sel)
+            self.visits.accumulate(act, sel=self._vis_sel_u8, period=self._period)
+
+    def _begin(self, k):
+        """The start of an ``evaluate`` / ``record`` call: the quota, and the period of its samples."""
+        self.quota.fill_(k)
+        if self.visits is not None:
+            self._period = 0 if int(self.tr.episode.min()) <= self.visits.explore_until else 1
+
     @torch.no_grad()
     def _step(self, p):
         """One eval step from buffer parity p: act without noise (the learner's noise counter does not
@@ -86,6 +115,7 @@ class Evaluator:
         c, n = self.bufs[p], self.bufs[1 - p]
         if self.uam:
             act = self.model.act(c.own, c.radar, self.episode, noisy=False)
+            self._visit(act)
             self.env.step(act, out=n)
             self.stats.accumulate(n, quota=self.quota)
             if self.ledger is not None:
@@ -94,11 +124,13 @@ class Evaluator:
             return
         elif self.gru:
             act, hn, _ = self._acts[p](None)
+            self._visit(act)
             # a new episode starts from a zero hidden state, as in training (WGRU/ma_main:476-478)
             self.env.step_tail(act, out=n, replay=None, zero_rows=hn)
             self.stats.accumulate(n, quota=self.quota)
         else:
             act = self.model.act(c.own, c.radar, c.nei, self.episode, noisy=False)
+            self._visit(act)
             self.env.step_tail(act, out=n, replay=None)
             self.stats.accumulate(n, quota=self.quota)
         if self.ledger is not None:
@@ -117,6 +149,7 @@ class Evaluator:
             act, hn, _ = self._acts[p](None)
         else:
             act = self.model.act(c.own, c.radar, c.nei, self.episode, noisy=False)
+        self._visit(act)
         self.env.step(act, out=n)
         self._rec.after_step(n, act)
         self.stats.accumulate(n, quota=self.quota)
@@ -147,18 +180,20 @@ class Evaluator:
         k = int(episodes_per_env)
         assert k >= 1
         use_graph = not _trainer.NO_GRAPH
-        if use_graph and self._graphs is None:
-            self._graphs = self._capture()
+        self._begin(k)
+        if use_graph and self._period not in self._graphs:
+            self._graphs[self._period] = self._capture()
         self._start()
         self.stats.reset()
         if self.ledger is not None:
             self.ledger.reset()
-        self.quota.fill_(k)
+        if self.visits is not None:
+            self.visits.reset()
         # an episode takes at most episode_length + 1 steps (timeout: episode_length < len)
         most = k * (self.episode_length + 1)
         for s in range(most):
             if use_graph:
-                self._graphs[s & 1].replay()
+                self._graphs[self._period][s & 1].replay()
             else:
                 self._step(s & 1)
             if (s + 1) % POLL == 0 and self.stats.under_quota() == 0:
@@ -184,7 +219,8 @@ class Evaluator:
         k = int(episodes_per_env)
         assert k >= 1
         S = int(steps) if steps is not None else k * (self.episode_length + 2)
-        key = (None if env_ids is None else tuple(int(e) for e in env_ids), S, k)
+        self._begin(k)
+        key = (None if env_ids is None else tuple(int(e) for e in env_ids), S, k, self._period)
         if self._rec_key != key:
             self._rec_graphs = None
             self._rec = FlightRecorder.for_env(self.env, env_ids, steps=S, episodes=k)
@@ -197,7 +233,8 @@ class Evaluator:
         self.stats.reset()
         if self.ledger is not None:
             self.ledger.reset()
-        self.quota.fill_(k)
+        if self.visits is not None:
+            self.visits.reset()
         rec.reset()
         rec.after_reset(None)
         for s in range(k * (self.episode_length + 1)):

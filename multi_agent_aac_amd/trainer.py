@@ -76,6 +76,8 @@ class CheckpointMixin:
             extra.update({f"stats.{k}": v for k, v in self.stats.tensors().items()})
         if getattr(self, "monitor", None) is not None:
             extra.update({f"monitor.{k}": v for k, v in self.monitor.tensors().items()})
+        if getattr(self, "visits", None) is not None:
+            extra.update({f"visits.{k}": v for k, v in self.visits.tensors().items()})
         return dict(learner=self.model, replay=self.replay, env=self.env, extra=extra)
 
     def save_checkpoint(self, path):
@@ -99,6 +101,15 @@ class CheckpointMixin:
             from .stats import EpisodeStats
             self.stats = EpisodeStats.for_env(self.env)
 
+    def _init_visits(self, visits):
+        """``visits``: False / None (off), True (50 x 50 position bins, 20 x 20 action bins, the model's
+        default noise period) or a dict of ``VisitMap`` keywords (grid, act_bins, explore_until)."""
+        self.visits = None
+        if visits:
+            from .visits import VisitMap
+            kw = dict(visits) if isinstance(visits, dict) else {}
+            self.visits = VisitMap(self.env, **kw)
+
     def _init_monitor(self, monitor, A, dtype):
         """``monitor``: False / None (off), True (a ring of 64 updates) or a ring length.  Built and
         attached to the model before its first update plan."""
@@ -114,7 +125,8 @@ class CheckpointMixin:
         (``env.check_band_capacity``, where the env has one), that the learner monitor (if any) saw no
         non-finite update (``monitor.check()``: FloatingPointError naming the update), and returns the
         episode statistics (``stats.read()``; None without ``stats=True``), with the reward ledger's report
-        under ``"terms"`` where the trainer keeps one.  Synchronises."""
+        under ``"terms"`` and the exploration maps (``visits.VisitMap.read()``) under ``"visits"`` where the
+        trainer keeps them.  Synchronises."""
         if hasattr(self.env, "check_band_capacity"):
             self.env.check_band_capacity()
         if getattr(self, "monitor", None) is not None:
@@ -124,6 +136,8 @@ class CheckpointMixin:
             out = dict(out or {}, terms=self.ledger.read())
         if getattr(self.model, "clip", None) is not None:  # with gradient clipping: the model's clip record
             out = dict(out or {}, clip=self.model.clip_record())
+        if getattr(self, "visits", None) is not None:      # with exploration maps: their arrays
+            out = dict(out or {}, visits=self.visits.read())
         return out
 
     def terms(self):
@@ -161,10 +175,17 @@ class Trainer(CheckpointMixin):
     ``grad_clip`` (None, a bound, or a (critic, actor) pair) is the model's ``set_grad_clip``: each clipped
     network's Adam launches carry the reference's ``clip_grad_norm_``, eager or captured, and ``finish()``
     returns the record under ``"clip"``.  Off (the default) the launch lists are unchanged.  The record is
-    not checkpointed."""
+    not checkpointed.
+
+    ``visits=True`` (or a dict of ``visits.VisitMap`` keywords) keeps the exploration maps -- where the
+    fleet flew and which actions it took, split at the end of the noise schedule -- on the device in
+    ``self.visits``: one small launch between the act launch and the env step launch of every step, eager
+    or inside the whole-step graphs; ``finish()`` returns the arrays under ``"visits"``.  Off (the default)
+    not one launch or tensor changes and ``self.visits`` is None.  Its tensors are checkpointed as
+    ``visits.*`` under the same rules as ``stats.*``."""
 
     def __init__(self, E, N, B, memory, radar, seed, pg=None, model="att", maps=1, stats=False, monitor=False,
-                 terms=False, grad_clip=None):
+                 terms=False, grad_clip=None, visits=False):
         from . import world
         from .env import BatchedEnv
         from .maddpg import MADDPG
@@ -218,6 +239,7 @@ class Trainer(CheckpointMixin):
         if terms:       # the env's step launches take their terms form from here on (no graph exists yet)
             from .terms import RewardLedger
             self.ledger = RewardLedger.for_env(self.env)
+        self._init_visits(visits)
 
     def graph_ok(self):
         """Whole-step graphs: the fused env tail, one rank, the fused learner (ATT: AAC_STEP_GRAPH; the
@@ -240,6 +262,8 @@ class Trainer(CheckpointMixin):
             # the hidden-state pair flips with the buffer pair: parity p reads hp[p ^ hoff]
             hin, hout = self.hp[p ^ self._hoff], self.hp[1 - (p ^ self._hoff)]
             act, hn = self.model.act(c.own, c.radar, hin, self.episode, noisy=True, h_out=hout)
+            if self.visits is not None:
+                self.visits.accumulate(act)
             srcs = [c.own, c.radar, c.nei, act, n.reward, n.done, n.own, n.radar, n.nei, hin, hn]
             self.env.step_tail(act, out=n, replay=self.replay, srcs=srcs, zero_rows=hn,
                                pos_io=(self.pos_dev[p], self.pos_dev[1 - p]))
@@ -250,6 +274,8 @@ class Trainer(CheckpointMixin):
             self.model._plan(self.B).run()
             return
         act = self.model.act(c.own, c.radar, c.nei, self.episode, noisy=True)
+        if self.visits is not None:
+            self.visits.accumulate(act)
         srcs = [c.own, c.radar, c.nei, act, n.reward, n.done, n.own, n.radar, n.nei]
         self.env.step_tail(act, out=n, replay=self.replay, srcs=srcs, pos_io=(self.pos_dev[p], self.pos_dev[1 - p]))
         if self.stats is not None:
@@ -351,6 +377,8 @@ class Trainer(CheckpointMixin):
                 act, hn = self.model.act(c.own, c.radar, self.h, self.episode, noisy=True, h_out=hn_buf)
             else:
                 act = self.model.act(c.own, c.radar, c.nei, self.episode, noisy=True)
+            if self.visits is not None:      # the positions these actions are taken from
+                self.visits.accumulate(act)
         if time_env:
             ev0 = torch.cuda.Event(enable_timing=True)
             ev1 = torch.cuda.Event(enable_timing=True)
@@ -451,9 +479,13 @@ class UamTrainer(CheckpointMixin):
     ``self.ledger`` as ``Trainer``'s: one small launch after the stats launch position of every env step,
     eager or inside the whole-step graphs, on the main stream before the auto-reset forks to its side
     stream (the reset touches neither the terms nor ``env_done``).  Off (the default) the launches are
-    unchanged and ``self.ledger`` is None."""
+    unchanged and ``self.ledger`` is None.
+    ``visits=True`` (or a dict of ``visits.VisitMap`` keywords): the exploration maps in ``self.visits`` as
+    ``Trainer``'s: one small launch between the act launch and the env step launch, checkpointed as
+    ``visits.*`` and returned by ``finish()`` under ``"visits"``.  Off (the default) nothing changes."""
 
-    def __init__(self, E, N, B, memory, seed, pg=None, stats=False, monitor=False, terms=False, grad_clip=None):
+    def __init__(self, E, N, B, memory, seed, pg=None, stats=False, monitor=False, terms=False, grad_clip=None,
+                 visits=False):
         from . import uam, uam_learner
         if grad_clip is not None:      # not built for the float64 UAM learner: NotImplementedError
             uam_learner.unsupported_grad_clip()
@@ -483,6 +515,7 @@ class UamTrainer(CheckpointMixin):
         if terms:       # the env's step launches take their terms form from here on (no graph exists yet)
             from .terms import RewardLedger
             self.ledger = RewardLedger.for_uam(self.env)
+        self._init_visits(visits)
 
     def graph_ok(self):
         """Whole-step graphs: one rank, the fused learner, the replay past one batch, no hooks."""
@@ -499,6 +532,8 @@ class UamTrainer(CheckpointMixin):
         fused learner's raw launches."""
         c, n = self.bufs[p], self.bufs[1 - p]
         act = self.model.act(c.own, c.radar, self.episode, noisy=True)
+        if self.visits is not None:
+            self.visits.accumulate(act)
         self.env.step(act, out=n)
         if self.stats is not None:
             self.stats.accumulate(n)
@@ -580,6 +615,8 @@ class UamTrainer(CheckpointMixin):
             f(self)
         with trace.range("act"):
             act = self.model.act(c.own, c.radar, self.episode, noisy=True)
+            if self.visits is not None:
+                self.visits.accumulate(act)
         if time_env:
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ev0.record()
