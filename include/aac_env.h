@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "aac_record.h"
+#include "aac_sortie.h"
 #include "aac_visits.h"
 
 #ifdef __cplusplus
@@ -172,6 +173,14 @@ int aac_env_record(aac_env *env, const aac_record_state *state, const aac_record
  * between the act launch and the step launch it counts the position each action is taken from.
  * state->n_maps must be the handle's n_maps.  One launch on ``stream``, capturable. */
 int aac_env_visits(aac_env *env, const aac_visits_state *state, const aac_visits_step *step, void *stream);
+
+/* Sortie statistics (aac_sortie.h): aac_sortie_accumulate with E, N, pos, start, goal (the final
+ * destination) and the episode counter (wherever aac_env_use_episode_buffer has put it) filled from the
+ * handle's live device pointers at call time; the rest of ``step`` is the caller's.  Called after
+ * aac_env_step and before aac_env_auto_reset: the terminal positions must still be in the state, so a
+ * fused aac_env_step_tail(auto_reset = 1) leaves nothing to call it on.  One launch on ``stream`` (two
+ * with a log), capturable. */
+int aac_env_sorties(aac_env *env, const aac_sortie_state *state, const aac_sortie_step *step, void *stream);
 
 /* State export / import (device pointers, each may be NULL to skip).  `start` (double2[E][N]) is
  * the episode start: the reference-path origin of the WGRU variant's cross-track reward

@@ -100,6 +100,12 @@ int aac_uam_record(aac_uam *env, const aac_record_state *state, const aac_record
  * ``stream``, capturable. */
 int aac_uam_visits(aac_uam *env, const aac_visits_state *state, const aac_visits_step *step, void *stream);
 
+/* Sortie statistics (aac_sortie.h): aac_sortie_accumulate with E, N, pos, start, goal and the episode
+ * counter filled from the handle's live device pointers at call time; the rest of ``step`` is the
+ * caller's.  Called after aac_uam_step and before aac_uam_auto_reset.  One launch on ``stream`` (two with
+ * a log), capturable. */
+int aac_uam_sorties(aac_uam *env, const aac_sortie_state *state, const aac_sortie_step *step, void *stream);
+
 /* Host: draw n episodes with the reference's rules (UAM/env:575-747, UAM/util:165-237): cloud
  * choices, starts in the two start zones re-drawn until > 3 pB from earlier starts, ends uniform
  * over the no-spawn-subtracted regions on the start's side of the runway. */

@@ -30,6 +30,7 @@ EXPORTS = (
     "aac_uam_reward_map",
     "aac_uam_probe",
     "aac_visits_last_error", "aac_visits_accumulate", "aac_env_visits", "aac_uam_visits",
+    "aac_sortie_last_error", "aac_sortie_accumulate", "aac_sortie_reduce", "aac_env_sorties", "aac_uam_sorties",
 )
 
 vp = ctypes.c_void_p
@@ -153,6 +154,20 @@ class VisitsStep(ctypes.Structure):        # aac_visits_step
                [(n, i32) for n in ("act_f64", "E", "N", "explore_until")]
 
 
+class SortieState(ctypes.Structure):       # aac_sortie_state (include/aac_sortie.h)
+    _fields_ = [(n, vp) for n in ("straight", "first_seg", "run_dist", "last_pos", "run_flags", "reach_step",
+                                  "run_len", "ep_count", "slots", "collide_hist")] + \
+               [("hist_len", i32), ("log", vp), ("log_len", i32)] + \
+               [(n, vp) for n in ("log_meta", "fin_flag", "fin_row", "fin_list")]
+
+
+class SortieStep(ctypes.Structure):        # aac_sortie_step
+    _fields_ = [(n, vp) for n in ("pos", "start", "goal", "episode", "done", "mask", "env_done", "quota")] + \
+               [(n, i32) for n in ("E", "N", "episode_length", "bound_bit", "obstacle_bit", "drone_bit", "goal_bit",
+                                   "pad")] + \
+               [("reach_margin", ctypes.c_double)]
+
+
 _lib = None
 
 
@@ -225,6 +240,13 @@ def lib():
         L.aac_visits_accumulate.argtypes = vis
         L.aac_env_visits.argtypes = [vp] + vis
         L.aac_uam_visits.argtypes = [vp] + vis
+    if hasattr(L, "aac_sortie_accumulate") or not os.environ.get("AAC_LIB"):
+        sor = [ctypes.POINTER(SortieState), ctypes.POINTER(SortieStep), vp]
+        L.aac_sortie_last_error.restype = ctypes.c_char_p
+        L.aac_sortie_accumulate.argtypes = sor
+        L.aac_sortie_reduce.argtypes = [ctypes.POINTER(SortieState), i32, vp, i32, vp]
+        L.aac_env_sorties.argtypes = [vp] + sor
+        L.aac_uam_sorties.argtypes = [vp] + sor
     for name in EXPORTS:
         if os.environ.get("AAC_LIB") and not hasattr(L, name):
             continue          # an A/B experiment build of an earlier revision

@@ -18,10 +18,10 @@ ARCH = os.environ.get("AAC_OFFLOAD_ARCH", "gfx950")
 
 SOURCES = ["csrc/aac_env.hip", "csrc/aac_learn.hip", "csrc/aac_fused.hip", "csrc/aac_gru.hip", "csrc/aac_mpe.hip",
            "csrc/aac_uam.hip", "csrc/aac_uam_actor.hip", "csrc/aac_uam_learn.hip", "csrc/aac_stats.hip",
-           "csrc/aac_record.hip", "csrc/aac_monitor.hip", "csrc/aac_terms.hip", "csrc/aac_clip.hip", "csrc/aac_visits.hip", "csrc/aac_host.cpp", "csrc/aac_trace.cpp"]
+           "csrc/aac_record.hip", "csrc/aac_monitor.hip", "csrc/aac_terms.hip", "csrc/aac_clip.hip", "csrc/aac_visits.hip", "csrc/aac_sortie.hip", "csrc/aac_host.cpp", "csrc/aac_trace.cpp"]
 HEADERS = ["include/aac_env.h", "include/aac_learn.h", "include/aac_fused.h", "include/aac_gru.h", "include/aac_mpe.h",
            "include/aac_uam.h", "include/aac_uam_learn.h", "include/aac_trace.h", "include/aac_stats.h",
-           "include/aac_record.h", "include/aac_monitor.h", "include/aac_terms.h", "include/aac_clip.h", "include/aac_probe.h", "include/aac_rmap.h", "include/aac_uam_rmap.h", "include/aac_uam_probe.h", "include/aac_visits.h", "multi_agent_aac_amd/csrc/aac_wave.h", "multi_agent_aac_amd/csrc/aac_geom.h",
+           "include/aac_record.h", "include/aac_monitor.h", "include/aac_terms.h", "include/aac_clip.h", "include/aac_probe.h", "include/aac_rmap.h", "include/aac_uam_rmap.h", "include/aac_uam_probe.h", "include/aac_visits.h", "include/aac_sortie.h", "multi_agent_aac_amd/csrc/aac_wave.h", "multi_agent_aac_amd/csrc/aac_geom.h",
            "multi_agent_aac_amd/csrc/aac_adam_bc.h", "multi_agent_aac_amd/csrc/aac_copysum.h",
            "multi_agent_aac_amd/csrc/aac_noise.h"]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function", f"--offload-arch={ARCH}"]

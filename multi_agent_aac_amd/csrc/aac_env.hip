@@ -2432,6 +2432,19 @@ int aac_env_visits(aac_env *h, const aac_visits_state *state, const aac_visits_s
     return AAC_OK;
 }
 
+int aac_env_sorties(aac_env *h, const aac_sortie_state *state, const aac_sortie_step *step, void *stream) {
+    if (!h || !state || !step) return fail(AAC_E_INVALID, "null argument");
+    aac_sortie_step p = *step;
+    p.E = h->cfg.E;
+    p.N = h->cfg.N;
+    p.pos = (const double *)h->pos;
+    p.start = (const double *)h->start;
+    p.goal = (const double *)h->goal;
+    p.episode = h->episode;
+    if (int rc = aac_sortie_accumulate(state, &p, stream)) return fail(rc, aac_sortie_last_error());
+    return AAC_OK;
+}
+
 int aac_env_probe(aac_env *h, const double *pos_dev, const int32_t *map_idx_dev, int64_t M, const uint8_t *sel_dev,
                   const aac_probe_out *out, void *stream) {
     if (!h || !out) return fail(AAC_E_INVALID, "null argument");

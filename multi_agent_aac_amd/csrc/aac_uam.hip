@@ -1853,6 +1853,19 @@ int aac_uam_visits(aac_uam *h, const aac_visits_state *state, const aac_visits_s
     return AAC_OK;
 }
 
+int aac_uam_sorties(aac_uam *h, const aac_sortie_state *state, const aac_sortie_step *step, void *stream) {
+    if (!h || !state || !step) return ufail(AAC_E_INVALID, "null argument");
+    aac_sortie_step p = *step;
+    p.E = h->cfg.E;
+    p.N = h->cfg.N;
+    p.pos = (const double *)h->pos;
+    p.start = (const double *)h->start;
+    p.goal = (const double *)h->goal;
+    p.episode = h->episode;
+    if (int rc = aac_sortie_accumulate(state, &p, stream)) return ufail(rc, aac_sortie_last_error());
+    return AAC_OK;
+}
+
 #define UCPY(dst, src, n)                                                                                   \
     if (dst && src) UCHK(hipMemcpyAsync((void *)(dst), (const void *)(src), (n), hipMemcpyDeviceToDevice,   \
                                         (hipStream_t)stream));

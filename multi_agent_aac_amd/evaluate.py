@@ -38,9 +38,20 @@ class Evaluator:
     goes into ONE period: the one the training loop is in, read at the start of the call from the
     TRAINING env's per-env episode counter (``trainer.episode``, the counter the noise schedule reads):
     "explore" while its minimum over the envs is ``<= explore_until``, i.e. until every training env has
-    left the noise schedule, "exploit" afterwards.  The read synchronises."""
+    left the noise schedule, "exploit" afterwards.  The read synchronises.
 
-    def __init__(self, trainer, E=None, seed=0, log=0, terms=False, visits=False):
+    ``sorties=True`` (or a dict of ``sorties.SortieStats`` keywords: log, reach_margin): ``self.sorties``
+    keeps the by-sortie report of the reference (UAM/main:1130-1144: every aircraft of every finished
+    episode in one class, the flight-distance ratio of those that reached their goals, the
+    steps-before-collision histogram), emptied at the start of every ``evaluate`` / ``record`` call, fed
+    under the same quota as ``self.stats`` (the same episode set) and read with ``self.sorties.read()``.
+    The accumulator needs the terminal positions, which the fused step tail has already reset, so with
+    sorties on the ATT and GRU rollouts of ``evaluate`` run the split launch sequence of ``record`` (act,
+    step, tallies, hidden-state zeroing, auto-reset): the same results, a few more launches a step.  The
+    return values of ``evaluate`` / ``record`` do not change; off (the default) not one launch or tensor
+    changes."""
+
+    def __init__(self, trainer, E=None, seed=0, log=0, terms=False, visits=False, sorties=False):
         self.tr, self.model = trainer, trainer.model
         tenv = trainer.env
         self.E, self.N = int(E or trainer.E), trainer.N
@@ -78,6 +89,11 @@ class Evaluator:
             self.visits = VisitMap(self.env, **(dict(visits) if isinstance(visits, dict) else {}))
             self._vis_sel = torch.zeros(self.E, dtype=torch.bool, device=dev)
             self._vis_sel_u8 = self._vis_sel.view(torch.uint8)
+        self.sorties = None
+        if sorties:
+            from .sorties import SortieStats
+            kw = dict(sorties) if isinstance(sorties, dict) else {}
+            self.sorties = (SortieStats.for_uam if self.uam else SortieStats.for_env)(self.env, **kw)
         if self.gru:
             from . import gru
             # hidden states as the trainer's ping-pong pair, and act plans of this object's own: the
@@ -113,6 +129,9 @@ class Evaluator:
         """One eval step from buffer parity p: act without noise (the learner's noise counter does not
         advance), env step with auto-reset and no replay push, tally."""
         c, n = self.bufs[p], self.bufs[1 - p]
+        if self.sorties is not None and not self.uam:
+            # the sortie accumulator reads the terminal positions: the split sequence, no recorder
+            return self._record_step(p, rec=None)
         if self.uam:
             act = self.model.act(c.own, c.radar, self.episode, noisy=False)
             self._visit(act)
@@ -120,6 +139,8 @@ class Evaluator:
             self.stats.accumulate(n, quota=self.quota)
             if self.ledger is not None:
                 self.ledger.accumulate(n, quota=self.quota)
+            if self.sorties is not None:
+                self.sorties.accumulate(n, quota=self.quota)
             self.env.auto_reset(n.env_done, out=n)
             return
         elif self.gru:
@@ -137,10 +158,12 @@ class Evaluator:
             self.ledger.accumulate(n, quota=self.quota)
 
     @torch.no_grad()
-    def _record_step(self, p):
+    def _record_step(self, p, rec=True):
         """``_step`` as separate launches, so that the recorder sees the terminal state before the reset
         and the fresh state after it: act, env step, record, tally, zero the finished envs' hidden
-        states, auto-reset, record the reset rows.  Same results as the fused tail."""
+        states, auto-reset, record the reset rows.  Same results as the fused tail.  ``rec=None``: the
+        same sequence without the recorder's launches (``evaluate`` with sorties on)."""
+        rec = self._rec if rec else None
         c, n = self.bufs[p], self.bufs[1 - p]
         hn = None
         if self.uam:
@@ -151,15 +174,19 @@ class Evaluator:
             act = self.model.act(c.own, c.radar, c.nei, self.episode, noisy=False)
         self._visit(act)
         self.env.step(act, out=n)
-        self._rec.after_step(n, act)
+        if rec is not None:
+            rec.after_step(n, act)
         self.stats.accumulate(n, quota=self.quota)
         if self.ledger is not None:
             self.ledger.accumulate(n, quota=self.quota)
+        if self.sorties is not None:
+            self.sorties.accumulate(n, quota=self.quota)
         if hn is not None:
             from . import gru
             gru.reset_hidden(hn, n.env_done)
         self.env.auto_reset(n.env_done, out=n)
-        self._rec.after_reset(n.env_done)
+        if rec is not None:
+            rec.after_reset(n.env_done)
 
     def _capture(self, step=None):
         # one eager step per parity first: act plans and buffers are built outside the captures
@@ -189,6 +216,8 @@ class Evaluator:
             self.ledger.reset()
         if self.visits is not None:
             self.visits.reset()
+        if self.sorties is not None:
+            self.sorties.reset()
         # an episode takes at most episode_length + 1 steps (timeout: episode_length < len)
         most = k * (self.episode_length + 1)
         for s in range(most):
@@ -235,6 +264,8 @@ class Evaluator:
             self.ledger.reset()
         if self.visits is not None:
             self.visits.reset()
+        if self.sorties is not None:
+            self.sorties.reset()
         rec.reset()
         rec.after_reset(None)
         for s in range(k * (self.episode_length + 1)):

@@ -78,6 +78,8 @@ class CheckpointMixin:
             extra.update({f"monitor.{k}": v for k, v in self.monitor.tensors().items()})
         if getattr(self, "visits", None) is not None:
             extra.update({f"visits.{k}": v for k, v in self.visits.tensors().items()})
+        if getattr(self, "sorties", None) is not None:
+            extra.update({f"sorties.{k}": v for k, v in self.sorties.tensors().items()})
         return dict(learner=self.model, replay=self.replay, env=self.env, extra=extra)
 
     def save_checkpoint(self, path):
@@ -110,6 +112,15 @@ class CheckpointMixin:
             kw = dict(visits) if isinstance(visits, dict) else {}
             self.visits = VisitMap(self.env, **kw)
 
+    def _init_sorties(self, sorties):
+        """``sorties``: False / None (off), True or a dict of ``SortieStats`` keywords (log, reach_margin).
+        UAM only: the ATT / GRU ``Trainer`` resets inside its fused step launch."""
+        self.sorties = None
+        if sorties:
+            from .sorties import SortieStats
+            kw = dict(sorties) if isinstance(sorties, dict) else {}
+            self.sorties = SortieStats.for_uam(self.env, **kw)
+
     def _init_monitor(self, monitor, A, dtype):
         """``monitor``: False / None (off), True (a ring of 64 updates) or a ring length.  Built and
         attached to the model before its first update plan."""
@@ -125,8 +136,9 @@ class CheckpointMixin:
         (``env.check_band_capacity``, where the env has one), that the learner monitor (if any) saw no
         non-finite update (``monitor.check()``: FloatingPointError naming the update), and returns the
         episode statistics (``stats.read()``; None without ``stats=True``), with the reward ledger's report
-        under ``"terms"`` and the exploration maps (``visits.VisitMap.read()``) under ``"visits"`` where the
-        trainer keeps them.  Synchronises."""
+        under ``"terms"``, the exploration maps (``visits.VisitMap.read()``) under ``"visits"`` and the
+        sortie statistics (``sorties.SortieStats.read()``) under ``"sorties"`` where the trainer keeps them.
+        Synchronises."""
         if hasattr(self.env, "check_band_capacity"):
             self.env.check_band_capacity()
         if getattr(self, "monitor", None) is not None:
@@ -138,6 +150,8 @@ class CheckpointMixin:
             out = dict(out or {}, clip=self.model.clip_record())
         if getattr(self, "visits", None) is not None:      # with exploration maps: their arrays
             out = dict(out or {}, visits=self.visits.read())
+        if getattr(self, "sorties", None) is not None:     # with sortie statistics: their report
+            out = dict(out or {}, sorties=self.sorties.read())
         return out
 
     def terms(self):
@@ -482,10 +496,17 @@ class UamTrainer(CheckpointMixin):
     unchanged and ``self.ledger`` is None.
     ``visits=True`` (or a dict of ``visits.VisitMap`` keywords): the exploration maps in ``self.visits`` as
     ``Trainer``'s: one small launch between the act launch and the env step launch, checkpointed as
-    ``visits.*`` and returned by ``finish()`` under ``"visits"``.  Off (the default) nothing changes."""
+    ``visits.*`` and returned by ``finish()`` under ``"visits"``.  Off (the default) nothing changes.
+    ``sorties=True`` (or a dict of ``sorties.SortieStats`` keywords): the by-sortie report (outcome class
+    of every aircraft of every finished episode, flight-distance ratio, steps-before-collision histogram)
+    in ``self.sorties``: one small launch beside the stats launch, between the env step and the auto-reset
+    (it reads the terminal positions), eager or inside the whole-step graphs; checkpointed as ``sorties.*``
+    under the rules of ``stats.*`` and returned by ``finish()`` under ``"sorties"``.  Off (the default)
+    nothing changes.  The ATT / GRU ``Trainer`` has no such option: its fused tail resets inside the step
+    launch; ``evaluate.Evaluator(sorties=True)`` covers all three."""
 
     def __init__(self, E, N, B, memory, seed, pg=None, stats=False, monitor=False, terms=False, grad_clip=None,
-                 visits=False):
+                 visits=False, sorties=False):
         from . import uam, uam_learner
         if grad_clip is not None:      # not built for the float64 UAM learner: NotImplementedError
             uam_learner.unsupported_grad_clip()
@@ -516,6 +537,7 @@ class UamTrainer(CheckpointMixin):
             from .terms import RewardLedger
             self.ledger = RewardLedger.for_uam(self.env)
         self._init_visits(visits)
+        self._init_sorties(sorties)
 
     def graph_ok(self):
         """Whole-step graphs: one rank, the fused learner, the replay past one batch, no hooks."""
@@ -539,6 +561,8 @@ class UamTrainer(CheckpointMixin):
             self.stats.accumulate(n)
         if self.ledger is not None:
             self.ledger.accumulate(n)
+        if self.sorties is not None:
+            self.sorties.accumulate(n)
         self.replay.push_batch(c.own, c.radar, act, n.reward, n.done, n.own, n.radar,
                                pos_io=(self.pos_dev[p], self.pos_dev[1 - p]))
         fu = self.model.fused(self.B, self.replay)
@@ -626,6 +650,8 @@ class UamTrainer(CheckpointMixin):
                 self.stats.accumulate(n)
             if self.ledger is not None:
                 self.ledger.accumulate(n)
+            if self.sorties is not None:
+                self.sorties.accumulate(n)
         if time_env:
             ev1.record()
             self.env_events.append((ev0, ev1))
