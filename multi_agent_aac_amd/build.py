@@ -23,7 +23,7 @@ HEADERS = ["include/aac_env.h", "include/aac_learn.h", "include/aac_fused.h", "i
            "include/aac_uam.h", "include/aac_uam_learn.h", "include/aac_trace.h", "include/aac_stats.h",
            "include/aac_record.h", "include/aac_monitor.h", "include/aac_terms.h", "include/aac_clip.h", "include/aac_probe.h", "include/aac_rmap.h", "include/aac_uam_rmap.h", "include/aac_uam_probe.h", "include/aac_visits.h", "include/aac_sortie.h", "multi_agent_aac_amd/csrc/aac_wave.h", "multi_agent_aac_amd/csrc/aac_geom.h",
            "multi_agent_aac_amd/csrc/aac_adam_bc.h", "multi_agent_aac_amd/csrc/aac_copysum.h",
-           "multi_agent_aac_amd/csrc/aac_noise.h"]
+           "multi_agent_aac_amd/csrc/aac_noise.h", "multi_agent_aac_amd/csrc/aac_slots.h"]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function", f"--offload-arch={ARCH}"]
 # roctx ranges (include/aac_trace.h) come from rocprofiler-sdk's roctx library, found at run time by rpath
 LINK = ["-L/opt/rocm/lib", "-lrocprofiler-sdk-roctx", "-Wl,-rpath,/opt/rocm/lib"]

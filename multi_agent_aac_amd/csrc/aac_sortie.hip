@@ -14,18 +14,18 @@
 //                       adds are gathered in an LDS histogram (up to 2048 bins; a longer one takes them
 //                       in global memory) and flushed with one 64-bit integer add per non-zero bin: many
 //                       envs end at the same length, and their adds would queue on one word in L2.
-// sortie_log_kernel     one workgroup: ordered list of the envs that finished (aacw::compact_flags),
-//                       their N rows each appended to the ring in that order.
-// sortie_reduce_kernel  one workgroup per 8-byte field: slots folded in a fixed order (thread t takes
-//                       slots t, t + 256, ... in order, then a fixed LDS tree).
+// sortie_log_kernel     one workgroup: the finished envs' N rows each appended to the ring in env order
+//                       (aacs::log_finished).
+// sortie_reduce_kernel  one workgroup per 8-byte field: slots folded in a fixed order (aacs::slot_reduce);
+//                       with clear it also empties collide_hist.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <string>
 
 #include "aac_env.h"
+#include "aac_slots.h"
 #include "aac_sortie.h"
-#include "aac_wave.h"
 
 namespace {
 
@@ -196,17 +196,7 @@ __global__ __launch_bounds__(NT) void sortie_accum_kernel(KArgs A, int AP) {
     s_d[3][t] = a_max;
     s_d[4][t] = a_flown;
     s_d[5][t] = a_straight;
-    for (int s = NT / 2; s > 0; s >>= 1) {
-        __syncthreads();
-        if (t < s) {
-            s_d[0][t] += s_d[0][t + s];
-            s_d[1][t] += s_d[1][t + s];
-            s_d[2][t] = fmin(s_d[2][t], s_d[2][t + s]);
-            s_d[3][t] = fmax(s_d[3][t], s_d[3][t + s]);
-            s_d[4][t] += s_d[4][t + s];
-            s_d[5][t] += s_d[5][t + s];
-        }
-    }
+    aacs::fold_tree<NT, 4>({s_d[0], s_d[1], s_d[4], s_d[5]}, s_d[2], s_d[3], t);
     __syncthreads();
     int64_t *slot = S.slots + (size_t)blockIdx.x * NF;
     double *slotd = (double *)slot;
@@ -222,59 +212,19 @@ __global__ __launch_bounds__(NT) void sortie_accum_kernel(KArgs A, int AP) {
 }
 
 __global__ __launch_bounds__(1024) void sortie_log_kernel(aac_sortie_state S, int E, int N) {
-    aacw::compact_flags(S.fin_flag, E, S.fin_list);
-    __syncthreads();
-    const int64_t n = (int64_t)S.fin_list[0] * N, L = S.log_len;
-    const int64_t pos = S.log_meta[0], calls = S.log_meta[1];
-    // more rows than the ring holds: only the last L of them stay
-    for (int64_t k = threadIdx.x; k < n; k += 1024) {
-        if (k < n - L) continue;
-        const int j = (int)(k / N), i = (int)(k - (int64_t)j * N);
-        S.log[(pos + k) % L] = S.fin_row[(size_t)S.fin_list[1 + j] * N + i];
-    }
-    __syncthreads();      // every thread has read log_meta
-    if (threadIdx.x == 0) {
-        S.log_meta[0] = pos + n;
-        S.log_meta[1] = calls + 1;
-    }
+    aacs::log_finished(S, E, N, [](aac_sortie_row &, int64_t) {});
+}
+
+constexpr aacs::Kind field_kind(int f) {
+    return f < F_SUM ? aacs::INT_SUM : f == F_MIN ? aacs::DBL_MIN : f == F_MAX ? aacs::DBL_MAX : aacs::DBL_SUM;
 }
 
 __global__ __launch_bounds__(256) void sortie_reduce_kernel(int64_t *slots, int G, int64_t *totals, int clear,
                                                              int64_t *hist, int hist_len) {
-    __shared__ int64_t s_i[256];
-    __shared__ double s_d[256];
-    const int f = blockIdx.x, t = threadIdx.x;
-    const bool is_d = f >= F_SUM;
-    int64_t ai = 0;
-    double ad = f == F_MIN ? INFINITY : f == F_MAX ? -INFINITY : 0.0;
-    for (int g = t; g < G; g += 256) {
-        int64_t *p = slots + (size_t)g * NF + f;
-        if (is_d) {
-            const double v = *(double *)p;
-            ad = f == F_MIN ? fmin(ad, v) : f == F_MAX ? fmax(ad, v) : ad + v;
-            if (clear) *(double *)p = f == F_MIN ? INFINITY : f == F_MAX ? -INFINITY : 0.0;
-        } else {
-            ai += *p;
-            if (clear) *p = 0;
-        }
-    }
+    // the histogram is emptied beside the fold: no ordering between the two
     if (clear)
-        for (int j = f * 256 + t; j < hist_len; j += NF * 256) hist[j] = 0;
-    s_i[t] = ai;
-    s_d[t] = ad;
-    for (int s = 128; s > 0; s >>= 1) {
-        __syncthreads();
-        if (t < s) {
-            s_i[t] += s_i[t + s];
-            s_d[t] = f == F_MIN ? fmin(s_d[t], s_d[t + s]) : f == F_MAX ? fmax(s_d[t], s_d[t + s]) : s_d[t] + s_d[t + s];
-        }
-    }
-    if (t == 0) {
-        if (is_d)
-            ((double *)totals)[f] = s_d[0];
-        else
-            totals[f] = s_i[0];
-    }
+        for (int j = blockIdx.x * 256 + threadIdx.x; j < hist_len; j += NF * 256) hist[j] = 0;
+    aacs::slot_reduce<NF, field_kind>(slots, G, totals, clear);
 }
 
 int check_state(const aac_sortie_state *s, const char *what) {

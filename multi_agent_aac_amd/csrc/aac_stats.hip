@@ -8,18 +8,17 @@
 //                      fixed LDS tree (thread order) and added to the workgroup's own slot, which no
 //                      other workgroup touches: no floating-point atomics, no ordering between
 //                      workgroups, so the slots do not depend on scheduling.
-// stats_log_kernel     one workgroup: ordered list of the envs that finished (aacw::compact_flags),
-//                      their rows appended to the ring in that order.
-// stats_reduce_kernel  one workgroup per 8-byte field: slots folded in a fixed order (thread t takes
-//                      slots t, t + 256, ... in order, then a fixed LDS tree).
+// stats_log_kernel     one workgroup: the finished envs' rows appended to the ring in env order, stamped
+//                      with the step (aacs::log_finished).
+// stats_reduce_kernel  one workgroup per 8-byte field: slots folded in a fixed order (aacs::slot_reduce).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <string>
 
 #include "aac_env.h"
+#include "aac_slots.h"
 #include "aac_stats.h"
-#include "aac_wave.h"
 
 namespace {
 
@@ -171,15 +170,7 @@ __global__ __launch_bounds__(NT) void stats_accum_kernel(KArgs A) {
         r_min[t] = fin ? ret : INFINITY;
         r_max[t] = fin ? ret : -INFINITY;
     }
-    for (int s = EPW / 2; s > 0; s >>= 1) {
-        __syncthreads();
-        if (t < s) {
-            r_sum[t] += r_sum[t + s];
-            r_sq[t] += r_sq[t + s];
-            r_min[t] = fmin(r_min[t], r_min[t + s]);
-            r_max[t] = fmax(r_max[t], r_max[t + s]);
-        }
-    }
+    aacs::fold_tree<EPW, 2>({r_sum, r_sq}, r_min, r_max, t);
     __syncthreads();
     double *slotd = (double *)slot;
     if (t < C_N) {
@@ -198,58 +189,21 @@ __global__ __launch_bounds__(NT) void stats_accum_kernel(KArgs A) {
 }
 
 __global__ __launch_bounds__(1024) void stats_log_kernel(aac_stats_state S, int E, int64_t step_index) {
-    aacw::compact_flags(S.fin_flag, E, S.fin_list);
-    __syncthreads();
-    const int n = S.fin_list[0], L = S.log_len;
-    const int64_t pos = S.log_meta[0], calls = S.log_meta[1];
-    const int64_t stepi = step_index < 0 ? calls : step_index;
-    // more rows than the ring holds: only the last L of them stay
-    for (int k = threadIdx.x; k < n; k += 1024) {
-        if (k < n - L) continue;
-        aac_stats_row row = S.fin_row[S.fin_list[1 + k]];
-        row.step = stepi;
-        S.log[(pos + k) % L] = row;
-    }
-    __syncthreads();      // every thread has read log_meta
-    if (threadIdx.x == 0) {
-        S.log_meta[0] = pos + n;
-        S.log_meta[1] = calls + 1;
-    }
+    // one row per env, stamped with the caller's step index or the calls so far
+    aacs::log_finished(S, E, 1,
+                       [=](aac_stats_row &row, int64_t calls) { row.step = step_index < 0 ? calls : step_index; });
+}
+
+constexpr aacs::Kind field_kind(int f) {
+    return f == F_UNDER ? aacs::INT_SUM_KEPT      // rewritten whole by every accumulate launch
+           : f == F_SUM || f == F_SQ ? aacs::DBL_SUM
+           : f == F_MIN ? aacs::DBL_MIN
+           : f == F_MAX ? aacs::DBL_MAX
+                        : aacs::INT_SUM;
 }
 
 __global__ __launch_bounds__(256) void stats_reduce_kernel(int64_t *slots, int G, int64_t *totals, int clear) {
-    __shared__ int64_t s_i[256];
-    __shared__ double s_d[256];
-    const int f = blockIdx.x, t = threadIdx.x;
-    const bool is_d = f >= F_SUM && f <= F_MAX;
-    int64_t ai = 0;
-    double ad = f == F_MIN ? INFINITY : f == F_MAX ? -INFINITY : 0.0;
-    for (int g = t; g < G; g += 256) {
-        int64_t *p = slots + (size_t)g * NF + f;
-        if (is_d) {
-            const double v = *(double *)p;
-            ad = f == F_MIN ? fmin(ad, v) : f == F_MAX ? fmax(ad, v) : ad + v;
-            if (clear) *(double *)p = f == F_MIN ? INFINITY : f == F_MAX ? -INFINITY : 0.0;
-        } else {
-            ai += *p;
-            if (clear && f != F_UNDER) *p = 0;
-        }
-    }
-    s_i[t] = ai;
-    s_d[t] = ad;
-    for (int s = 128; s > 0; s >>= 1) {
-        __syncthreads();
-        if (t < s) {
-            s_i[t] += s_i[t + s];
-            s_d[t] = f == F_MIN ? fmin(s_d[t], s_d[t + s]) : f == F_MAX ? fmax(s_d[t], s_d[t + s]) : s_d[t] + s_d[t + s];
-        }
-    }
-    if (t == 0) {
-        if (is_d)
-            ((double *)totals)[f] = s_d[0];
-        else
-            totals[f] = s_i[0];
-    }
+    aacs::slot_reduce<NF, field_kind>(slots, G, totals, clear);
 }
 
 int check_state(const aac_stats_state *s, const char *what) {

@@ -8,14 +8,14 @@
 //                      LDS and are folded over a fixed tree (thread order) into the workgroup's own slot,
 //                      which no other workgroup touches: no floating-point atomics, nothing depends on
 //                      scheduling.
-// terms_reduce_kernel  one workgroup per 8-byte field: slots folded in a fixed order (thread t takes
-//                      slots t, t + 256, ... in order, then the same tree).
+// terms_reduce_kernel  one workgroup per 8-byte field: slots folded in a fixed order (aacs::slot_reduce).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <string>
 
 #include "aac_env.h"
+#include "aac_slots.h"
 #include "aac_stats.h"
 #include "aac_terms.h"
 
@@ -80,15 +80,7 @@ __global__ __launch_bounds__(NT) void terms_accum_kernel(aac_terms_state S, aac_
         r_min[k][j] = fmin(fa ? a : INFINITY, fb ? b : INFINITY);
         r_max[k][j] = fmax(fa ? a : -INFINITY, fb ? b : -INFINITY);
     }
-    for (int s = HALF / 2; s > 0; s >>= 1) {
-        __syncthreads();
-        if (j < s) {
-            r_sum[k][j] += r_sum[k][j + s];
-            r_sq[k][j] += r_sq[k][j + s];
-            r_min[k][j] = fmin(r_min[k][j], r_min[k][j + s]);
-            r_max[k][j] = fmax(r_max[k][j], r_max[k][j + s]);
-        }
-    }
+    aacs::fold_tree<HALF, 2>({r_sum[k], r_sq[k]}, r_min[k], r_max[k], j);
     if (j == 0) {      // reads its own tree root
         int64_t *slot = S.slots + (size_t)g * NF;
         double *slotd = (double *)slot;
@@ -100,40 +92,12 @@ __global__ __launch_bounds__(NT) void terms_accum_kernel(aac_terms_state S, aac_
     }
 }
 
+constexpr aacs::Kind field_kind(int f) {
+    return f < F_SUM ? aacs::INT_SUM : f < F_MIN ? aacs::DBL_SUM : f < F_MAX ? aacs::DBL_MIN : aacs::DBL_MAX;
+}
+
 __global__ __launch_bounds__(256) void terms_reduce_kernel(int64_t *slots, int G, int64_t *totals, int clear) {
-    __shared__ int64_t s_i[256];
-    __shared__ double s_d[256];
-    const int f = blockIdx.x, t = threadIdx.x;
-    const bool is_min = f >= F_MIN && f < F_MAX, is_max = f >= F_MAX;
-    const double id = is_min ? INFINITY : is_max ? -INFINITY : 0.0;
-    int64_t ai = 0;
-    double ad = id;
-    for (int g = t; g < G; g += 256) {
-        int64_t *p = slots + (size_t)g * NF + f;
-        if (f) {
-            const double v = *(double *)p;
-            ad = is_min ? fmin(ad, v) : is_max ? fmax(ad, v) : ad + v;
-            if (clear) *(double *)p = id;
-        } else {
-            ai += *p;
-            if (clear) *p = 0;
-        }
-    }
-    s_i[t] = ai;
-    s_d[t] = ad;
-    for (int s = 128; s > 0; s >>= 1) {
-        __syncthreads();
-        if (t < s) {
-            s_i[t] += s_i[t + s];
-            s_d[t] = is_min ? fmin(s_d[t], s_d[t + s]) : is_max ? fmax(s_d[t], s_d[t + s]) : s_d[t] + s_d[t + s];
-        }
-    }
-    if (t == 0) {
-        if (f)
-            ((double *)totals)[f] = s_d[0];
-        else
-            totals[f] = s_i[0];
-    }
+    aacs::slot_reduce<NF, field_kind>(slots, G, totals, clear);
 }
 
 // one workgroup per track: the env's N rows are contiguous, copied as 16-B pieces

@@ -18,6 +18,7 @@ import torch
 from . import graphs as _graphs
 from . import trainer as _trainer
 from .stats import EpisodeStats
+from .tally import ACT, STEP, Tallies
 
 POLL = 16      # steps between two reads of the "envs still under quota" word
 
@@ -76,24 +77,27 @@ class Evaluator:
         dev = self.env.device
         self.episode = self.env.use_episode_buffer(torch.zeros(self.E, dtype=torch.int32, device=dev))
         self.bufs = [self.env.alloc_buffers(), self.env.alloc_buffers()]
-        self.stats = EpisodeStats.for_env(self.env, log=log)
         self.quota = torch.zeros(self.E, dtype=torch.int32, device=dev)
-        self.ledger = None
+        self.tally = Tallies()      # fed under the quota, emptied at the start of every call
+        self.stats = self.tally.add(EpisodeStats.for_env(self.env, log=log), STEP)
+        self.ledger = self.visits = self.sorties = None
+        self._period = None     # the period of this call's samples (None without a visit map)
         if terms:
             from .terms import RewardLedger
-            self.ledger = RewardLedger.for_uam(self.env) if self.uam else RewardLedger.for_env(self.env)
-        self.visits = self._vis_sel = None
-        self._period = None     # the period of this call's samples (None without a visit map)
+            self.ledger = self.tally.add((RewardLedger.for_uam if self.uam else RewardLedger.for_env)(self.env), STEP)
         if visits:
             from .visits import VisitMap
-            self.visits = VisitMap(self.env, **(dict(visits) if isinstance(visits, dict) else {}))
+            self.visits = self.tally.add(VisitMap(self.env, **(dict(visits) if isinstance(visits, dict) else {})), ACT)
             self._vis_sel = torch.zeros(self.E, dtype=torch.bool, device=dev)
             self._vis_sel_u8 = self._vis_sel.view(torch.uint8)
-        self.sorties = None
         if sorties:
             from .sorties import SortieStats
             kw = dict(sorties) if isinstance(sorties, dict) else {}
-            self.sorties = (SortieStats.for_uam if self.uam else SortieStats.for_env)(self.env, **kw)
+            self.sorties = self.tally.add((SortieStats.for_uam if self.uam else SortieStats.for_env)(self.env, **kw),
+                                          STEP)
+        # the sortie accumulator reads the terminal positions, which the fused step tail has already reset
+        self._split = self.sorties is not None and not self.uam
+        self._reads = [t.read for t in (self.stats, self.ledger) if t is not None]      # what a call returns
         if self.gru:
             from . import gru
             # hidden states as the trainer's ping-pong pair, and act plans of this object's own: the
@@ -114,14 +118,14 @@ class Evaluator:
     def _visit(self, act):
         """The visit map's launch, after the act launch: the envs still under their quota, as the
         statistics count them."""
-        if self.visits is not None:
+        if self.tally.act:
             torch.lt(self.stats.ep_count, self.quota, out=self._vis_sel)
-            self.visits.accumulate(act, sel=self._vis_sel_u8, period=self._period)
+            self.tally.after_act(act, sel=self._vis_sel_u8, period=self._period)
 
     def _begin(self, k):
         """The start of an ``evaluate`` / ``record`` call: the quota, and the period of its samples."""
         self.quota.fill_(k)
-        if self.visits is not None:
+        if self.tally.act:
             self._period = 0 if int(self.tr.episode.min()) <= self.visits.explore_until else 1
 
     @torch.no_grad()
@@ -129,33 +133,26 @@ class Evaluator:
         """One eval step from buffer parity p: act without noise (the learner's noise counter does not
         advance), env step with auto-reset and no replay push, tally."""
         c, n = self.bufs[p], self.bufs[1 - p]
-        if self.sorties is not None and not self.uam:
-            # the sortie accumulator reads the terminal positions: the split sequence, no recorder
+        if self._split:
+            # the split sequence, no recorder
             return self._record_step(p, rec=None)
         if self.uam:
             act = self.model.act(c.own, c.radar, self.episode, noisy=False)
             self._visit(act)
             self.env.step(act, out=n)
-            self.stats.accumulate(n, quota=self.quota)
-            if self.ledger is not None:
-                self.ledger.accumulate(n, quota=self.quota)
-            if self.sorties is not None:
-                self.sorties.accumulate(n, quota=self.quota)
+            self.tally.after_step(n, self.quota)
             self.env.auto_reset(n.env_done, out=n)
             return
-        elif self.gru:
+        if self.gru:
             act, hn, _ = self._acts[p](None)
             self._visit(act)
             # a new episode starts from a zero hidden state, as in training (WGRU/ma_main:476-478)
             self.env.step_tail(act, out=n, replay=None, zero_rows=hn)
-            self.stats.accumulate(n, quota=self.quota)
         else:
             act = self.model.act(c.own, c.radar, c.nei, self.episode, noisy=False)
             self._visit(act)
             self.env.step_tail(act, out=n, replay=None)
-            self.stats.accumulate(n, quota=self.quota)
-        if self.ledger is not None:
-            self.ledger.accumulate(n, quota=self.quota)
+        self.tally.after_step(n, self.quota)
 
     @torch.no_grad()
     def _record_step(self, p, rec=True):
@@ -176,11 +173,7 @@ class Evaluator:
         self.env.step(act, out=n)
         if rec is not None:
             rec.after_step(n, act)
-        self.stats.accumulate(n, quota=self.quota)
-        if self.ledger is not None:
-            self.ledger.accumulate(n, quota=self.quota)
-        if self.sorties is not None:
-            self.sorties.accumulate(n, quota=self.quota)
+        self.tally.after_step(n, self.quota)
         if hn is not None:
             from . import gru
             gru.reset_hidden(hn, n.env_done)
@@ -211,13 +204,7 @@ class Evaluator:
         if use_graph and self._period not in self._graphs:
             self._graphs[self._period] = self._capture()
         self._start()
-        self.stats.reset()
-        if self.ledger is not None:
-            self.ledger.reset()
-        if self.visits is not None:
-            self.visits.reset()
-        if self.sorties is not None:
-            self.sorties.reset()
+        self.tally.reset()
         # an episode takes at most episode_length + 1 steps (timeout: episode_length < len)
         most = k * (self.episode_length + 1)
         for s in range(most):
@@ -227,7 +214,8 @@ class Evaluator:
                 self._step(s & 1)
             if (s + 1) % POLL == 0 and self.stats.under_quota() == 0:
                 break
-        return self.stats.read() if self.ledger is None else (self.stats.read(), self.ledger.read())
+        out = [read() for read in self._reads]
+        return out[0] if len(out) == 1 else tuple(out)
 
     def record(self, episodes_per_env=1, env_ids=None, steps=None):
         """``evaluate(k)`` with a flight recorder on the envs ``env_ids`` (None: all): the same episode
@@ -237,9 +225,8 @@ class Evaluator:
         ``evaluate`` and its graphs are not involved."""
         steps_run = self._record_rollout(episodes_per_env, env_ids, steps)
         assert steps_run > 0
-        if self.ledger is not None:
-            return self.stats.read(), self._rec.read(), self.ledger.read()
-        return self.stats.read(), self._rec.read()
+        out = [read() for read in self._reads]
+        return tuple(out[:1] + [self._rec.read()] + out[1:])
 
     def _record_rollout(self, episodes_per_env=1, env_ids=None, steps=None):
         """The device part of ``record``: nothing is downloaded but the poll word.  Returns the number
@@ -259,13 +246,7 @@ class Evaluator:
         if use_graph and self._rec_graphs is None:
             self._rec_graphs = self._capture(self._record_step)
         self._start()
-        self.stats.reset()
-        if self.ledger is not None:
-            self.ledger.reset()
-        if self.visits is not None:
-            self.visits.reset()
-        if self.sorties is not None:
-            self.sorties.reset()
+        self.tally.reset()
         rec.reset()
         rec.after_reset(None)
         for s in range(k * (self.episode_length + 1)):

@@ -22,6 +22,7 @@ import torch
 
 from . import _native
 from .fused import adam4_order  # noqa: F401  (the order field of a vec job that follows adam_sum / sum_partials)
+from .tally import check, stream
 
 FIELDS = 27           # AAC_MONITOR_FIELDS
 VEC_WG = 64           # AAC_MONITOR_VEC_WG
@@ -35,16 +36,6 @@ FIELD_NAMES = ("loss_q", "loss_a", "q_mean", "q_min", "q_max", "y_mean", "y_min"
     f"{net}_{what}_{k}" for net in NETS for what in ("grad", "param") for k in ("sumsq", "absmax", "nonfinite"))
 assert len(FIELD_NAMES) == FIELDS
 COUNT_FIELDS = tuple(i for i, n in enumerate(FIELD_NAMES) if n.endswith("nonfinite"))
-
-
-def _chk(rc, what):
-    if rc != 0:
-        msg = _native.lib().aac_monitor_last_error().decode(errors="replace")
-        raise RuntimeError(f"{what} failed ({rc}): {msg}")
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 class VecLaunch:
@@ -67,9 +58,9 @@ class VecLaunch:
         self._fn = _native.lib().aac_monitor_vec
 
     def __call__(self):
-        rc = self._fn(self.arr, len(self.reads), self.f64, _stream())
+        rc = self._fn(self.arr, len(self.reads), self.f64, stream())
         if rc != 0:
-            _chk(rc, "aac_monitor_vec")
+            check(rc, "aac_monitor_vec", "aac_monitor_last_error")
 
 
 class CommitLaunch:
@@ -95,9 +86,9 @@ class CommitLaunch:
         self._fn = _native.lib().aac_monitor_commit
 
     def __call__(self):
-        rc = self._fn(self._ref, _stream())
+        rc = self._fn(self._ref, stream())
         if rc != 0:
-            _chk(rc, "aac_monitor_commit")
+            check(rc, "aac_monitor_commit", "aac_monitor_last_error")
 
 
 def unwrap(counter, ring, ring_update, agg, bad):

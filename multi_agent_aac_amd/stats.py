@@ -14,13 +14,13 @@ Counters and the reference's names (ATT/main):
   reach_hist[1]     one_drone_reach               reach_hist[2]           two_drone_reach
   reach_hist[N]     all_drone_reach               timeout / crash / goal  the branch of :448-462 taken
 """
-import ctypes
 import math
 
 import numpy as np
 import torch
 
 from . import _native
+from .tally import SlotTally, check
 
 EPW = 256             # AAC_STATS_EPW: envs per workgroup (= per slot)
 FIELDS = 81           # AAC_STATS_FIELDS
@@ -33,17 +33,7 @@ ROW = np.dtype([("ret", "<f8"), ("step", "<i8"), ("len", "<i4"), ("env", "<i4"),
 assert ROW.itemsize == 32
 
 
-def _chk(rc, what):
-    if rc != 0:
-        msg = _native.lib().aac_stats_last_error().decode(errors="replace")
-        raise RuntimeError(f"{what} failed ({rc}): {msg}")
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-class EpisodeStats:
+class EpisodeStats(SlotTally):
     """Running per-env episode state + totals for E envs x N agents.
 
     reward_dtype  torch.float32 (``StepBuffers``) or torch.float64 (``UamBuffers``)
@@ -51,6 +41,10 @@ class EpisodeStats:
     return_mode   1: agent 0's reward (the team reward every agent carries); 0: the sum over agents
     log           > 0: keep the last ``log`` finished episodes as rows, in (step, env) order
     """
+    EPW, FIELDS, ROW = EPW, FIELDS, ROW
+    MIN, MAX = slice(F_MIN, F_MIN + 1), slice(F_MAX, F_MAX + 1)
+    STATE = ("run_return", "run_len", "run_reach", "ep_count", "slots")
+    REDUCE, ERROR = "aac_stats_reduce", "aac_stats_last_error"
 
     def __init__(self, E, N, episode_length, reward_dtype=torch.float32, goal_bit=5, return_mode=1, log=0,
                  device=None):
@@ -60,32 +54,13 @@ class EpisodeStats:
             raise ValueError("EpisodeStats: reward_dtype float32 or float64")
         self.E, self.N, self.episode_length = int(E), int(N), int(episode_length)
         self.reward_dtype, self.goal_bit, self.return_mode = reward_dtype, int(goal_bit), int(return_mode)
-        self.L = int(log)
         d = self.device = torch.device(device if device is not None else "cuda")
-        E, G = self.E, (self.E + EPW - 1) // EPW
-        i32, i64 = dict(dtype=torch.int32, device=d), dict(dtype=torch.int64, device=d)
-        self.run_return = torch.zeros(E, dtype=torch.float64, device=d)
-        self.run_len = torch.zeros(E, **i32)
-        self.run_reach = torch.zeros(E, **i64)          # uint64 bit sets
-        self.ep_count = torch.zeros(E, **i32)
-        self.slots = torch.zeros(G, FIELDS, **i64)
-        self.totals = torch.zeros(FIELDS, **i64)
-        self.quota = torch.zeros(E, **i32)              # used by accumulate(quota=<int>)
-        self.log = self.log_meta = None
-        st = _native.StatsState()
-        if self.L:
-            self.log = torch.zeros(self.L, ROW.itemsize, dtype=torch.uint8, device=d)
-            self.log_meta = torch.zeros(2, **i64)
-            self._fin = (torch.zeros(E, dtype=torch.uint8, device=d),
-                         torch.zeros(E, ROW.itemsize, dtype=torch.uint8, device=d), torch.zeros(E + 1, **i32))
-            st.log, st.log_len, st.log_meta = self.log.data_ptr(), self.L, self.log_meta.data_ptr()
-            st.fin_flag, st.fin_row, st.fin_list = (t.data_ptr() for t in self._fin)
-        st.run_return, st.run_len = self.run_return.data_ptr(), self.run_len.data_ptr()
-        st.run_reach, st.ep_count, st.slots = self.run_reach.data_ptr(), self.ep_count.data_ptr(), self.slots.data_ptr()
-        self._st, self._st_ref = st, ctypes.byref(st)
+        self.run_return = torch.zeros(self.E, dtype=torch.float64, device=d)
+        self.run_len = torch.zeros(self.E, dtype=torch.int32, device=d)
+        self.run_reach = torch.zeros(self.E, dtype=torch.int64, device=d)          # uint64 bit sets
+        self.ep_count = torch.zeros(self.E, dtype=torch.int32, device=d)
         self._accumulate = _native.lib().aac_stats_accumulate
-        self._steps = {}        # id(bufs), quota pointer -> StatsStep
-        self.reset()
+        self._alloc(_native.StatsState(), log)
 
     @classmethod
     def for_env(cls, env, log=0):
@@ -98,71 +73,35 @@ class EpisodeStats:
         return cls(env.E, env.N, ep, torch.float32, goal_bit=5, return_mode=1 if env.cfg.team_reward else 0,
                    log=log, device=env.device)
 
-    # ------------------------------------------------------------------- state
-    def reset(self):
-        """Empty totals, running state, episode counts and log."""
-        for t in (self.run_return, self.run_len, self.run_reach, self.ep_count, self.slots):
-            t.zero_()
-        sd = self.slots.view(torch.float64)
-        sd[:, F_MIN] = math.inf
-        sd[:, F_MAX] = -math.inf
-        if self.L:
-            self.log.zero_()
-            self.log_meta.zero_()
-
-    def tensors(self):
-        """The device tensors a checkpoint must carry (loaded in place)."""
-        t = {"run_return": self.run_return, "run_len": self.run_len, "run_reach": self.run_reach,
-             "ep_count": self.ep_count, "slots": self.slots}
-        if self.L:
-            t["log"], t["log_meta"] = self.log, self.log_meta
-        return t
-
-    # ------------------------------------------------------------------- calls
     def accumulate(self, bufs, quota=None, step_index=-1):
         """Tally the step whose outputs are in ``bufs`` (a ``StepBuffers`` / ``UamBuffers``), after the
         step launch on the same stream.  ``quota``: int32 [E] tensor (or an int, kept in
         ``self.quota``): an env with that many finished episodes contributes nothing more.
         ``step_index`` >= 0 is logged with the rows instead of the device's call count.  A buffer
         set's tensors are taken as fixed: its launch arguments are built on the first call."""
-        if isinstance(quota, int):
-            self.quota.fill_(quota)
-            quota = self.quota
-        # the arguments of a buffer set are built once (the loops alternate two sets): the call itself
-        # is a dictionary lookup and the launch
-        key = (id(bufs), None if quota is None else quota.data_ptr(), step_index)
-        hit = self._steps.get(key)
-        if hit is None or hit[0] is not bufs:
-            r = bufs.reward
-            if r.dtype != self.reward_dtype or tuple(r.shape) != (self.E, self.N) or not r.is_contiguous():
-                raise ValueError(f"reward {tuple(r.shape)} {r.dtype}: expected ({self.E}, {self.N}) {self.reward_dtype}")
-            for name, shape in (("done", (self.E, self.N)), ("mask", (self.E, self.N)), ("env_done", (self.E,)),
-                                ("bbc", (self.E, 4))):
-                t = getattr(bufs, name)
-                if t.dtype != torch.uint8 or tuple(t.shape) != shape or not t.is_contiguous():
-                    raise ValueError(f"{name} {tuple(t.shape)} {t.dtype}: expected {shape} uint8")
-            if quota is not None and (quota.dtype != torch.int32 or tuple(quota.shape) != (self.E,)
-                                      or not quota.is_contiguous()):
-                raise ValueError("quota: int32 [E]")
-            p = _native.StatsStep()
-            p.reward, p.reward_f64 = r.data_ptr(), int(r.dtype == torch.float64)
-            p.done, p.mask = bufs.done.data_ptr(), bufs.mask.data_ptr()
-            p.env_done, p.bbc = bufs.env_done.data_ptr(), bufs.bbc.data_ptr()
-            p.E, p.N, p.episode_length = self.E, self.N, self.episode_length
-            p.goal_bit, p.return_mode = self.goal_bit, self.return_mode
-            p.quota = None if quota is None else quota.data_ptr()
-            p.step_index = int(step_index)
-            if len(self._steps) > 64:
-                self._steps.clear()
-            hit = self._steps[key] = (bufs, ctypes.byref(p), quota, p)
-        rc = self._accumulate(self._st_ref, hit[1], torch.cuda.current_stream().cuda_stream)
+        args = self._args(bufs, self._quota(quota), (step_index,))
+        rc = self._accumulate(self._st_ref, args, torch.cuda.current_stream().cuda_stream)
         if rc != 0:
-            _chk(rc, "aac_stats_accumulate")
+            check(rc, "aac_stats_accumulate", self.ERROR)
 
-    def _reduce(self, clear=False):
-        _chk(_native.lib().aac_stats_reduce(ctypes.byref(self._st), self.E, ctypes.c_void_p(self.totals.data_ptr()),
-                                            int(bool(clear)), _stream()), "aac_stats_reduce")
-        return self.totals.cpu().numpy()
+    def _build(self, bufs, quota, step_index):
+        r = bufs.reward
+        if r.dtype != self.reward_dtype or tuple(r.shape) != (self.E, self.N) or not r.is_contiguous():
+            raise ValueError(f"reward {tuple(r.shape)} {r.dtype}: expected ({self.E}, {self.N}) {self.reward_dtype}")
+        for name, shape in (("done", (self.E, self.N)), ("mask", (self.E, self.N)), ("env_done", (self.E,)),
+                            ("bbc", (self.E, 4))):
+            t = getattr(bufs, name)
+            if t.dtype != torch.uint8 or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"{name} {tuple(t.shape)} {t.dtype}: expected {shape} uint8")
+        p = _native.StatsStep()
+        p.quota = self._quota_ptr(quota)
+        p.reward, p.reward_f64 = r.data_ptr(), int(r.dtype == torch.float64)
+        p.done, p.mask = bufs.done.data_ptr(), bufs.mask.data_ptr()
+        p.env_done, p.bbc = bufs.env_done.data_ptr(), bufs.bbc.data_ptr()
+        p.E, p.N, p.episode_length = self.E, self.N, self.episode_length
+        p.goal_bit, p.return_mode = self.goal_bit, self.return_mode
+        p.step_index = int(step_index)
+        return p
 
     def under_quota(self):
         """Envs whose finished-episode count was below its quota after the last ``accumulate``
@@ -189,13 +128,3 @@ class EpisodeStats:
             out[k.replace("_count", "") + "_rate"] = out[k] / n if n else math.nan
         out["all_reach_rate"] = out["reach_hist"][self.N] / n if n else math.nan
         return out
-
-    def log_rows(self):
-        """The logged episodes, oldest first, as a numpy record array (fields of ``ROW``)."""
-        if not self.L:
-            return np.zeros(0, dtype=ROW)
-        n = int(self.log_meta[0])
-        rows = self.log.cpu().numpy().view(ROW).reshape(-1)
-        if n <= self.L:
-            return rows[:n].copy()
-        return np.roll(rows, -(n % self.L)).copy()

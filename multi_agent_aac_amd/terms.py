@@ -14,13 +14,13 @@ coefficients in effect for each aircraft.  The MPE env emits
 no terms; with several ranks each rank keeps its own ledger; a checkpoint does not carry the ledger (a
 resumed run starts an empty one).
 """
-import ctypes
 import math
 
 import numpy as np
 import torch
 
 from . import _native
+from .tally import SlotTally, check
 
 EPW = 256             # AAC_STATS_EPW: envs per workgroup (= per slot)
 WIDTH = 12            # AAC_TERMS_W
@@ -39,34 +39,20 @@ def names():
     return _names
 
 
-def _chk(rc, what):
-    if rc != 0:
-        msg = _native.lib().aac_terms_last_error().decode(errors="replace")
-        raise RuntimeError(f"{what} failed ({rc}): {msg}")
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-class RewardLedger:
+class RewardLedger(SlotTally):
     """Per-episode totals of the reward terms of E envs x N agents."""
+    EPW, FIELDS = EPW, FIELDS
+    MIN, MAX = slice(F_MIN, F_MAX), slice(F_MAX, FIELDS)
+    STATE = ("run", "ep_count", "slots")
+    REDUCE, ERROR = "aac_terms_reduce", "aac_terms_last_error"
 
     def __init__(self, env):
         self.env, self.E, self.N = env, env.E, env.N
         d = self.device = env.device
-        E, G = self.E, (self.E + EPW - 1) // EPW
-        self.run = torch.zeros(E, self.N, SLOTS, dtype=torch.float64, device=d)
-        self.ep_count = torch.zeros(E, dtype=torch.int32, device=d)
-        self.slots = torch.zeros(G, FIELDS, dtype=torch.int64, device=d)
-        self.totals = torch.zeros(FIELDS, dtype=torch.int64, device=d)
-        self.quota = torch.zeros(E, dtype=torch.int32, device=d)      # used by accumulate(quota=<int>)
-        st = _native.TermsState()
-        st.run, st.ep_count, st.slots = self.run.data_ptr(), self.ep_count.data_ptr(), self.slots.data_ptr()
-        self._st, self._st_ref = st, ctypes.byref(st)
+        self.run = torch.zeros(self.E, self.N, SLOTS, dtype=torch.float64, device=d)
+        self.ep_count = torch.zeros(self.E, dtype=torch.int32, device=d)
         self._accumulate = _native.lib().aac_terms_accumulate
-        self._steps = {}        # id(bufs), quota pointer, terms pointer -> TermsStep
-        self.reset()
+        self._alloc(_native.TermsState())
 
     @classmethod
     def for_env(cls, env):
@@ -90,49 +76,30 @@ class RewardLedger:
             env.use_terms_buffer()
         return cls(env)
 
-    def reset(self):
-        """Empty totals, running sums and episode counts."""
-        for t in (self.run, self.ep_count, self.slots):
-            t.zero_()
-        sd = self.slots.view(torch.float64)
-        sd[:, F_MIN:F_MAX] = math.inf
-        sd[:, F_MAX:] = -math.inf
-
     def accumulate(self, bufs, quota=None):
         """Add the step whose outputs are in ``bufs`` (``StepBuffers`` / ``UamBuffers``; its ``env_done`` is
         read) and whose terms are in the env's attached buffer, after the step launch on the same stream.
         ``quota``: int32 [E] tensor (or an int, kept in ``self.quota``), the rule of
         ``EpisodeStats.accumulate``: an env with that many finished episodes contributes nothing more."""
-        if isinstance(quota, int):
-            self.quota.fill_(quota)
-            quota = self.quota
+        quota = self._quota(quota)
         terms = self.env.terms
         if terms is None:
             raise RuntimeError("RewardLedger.accumulate: the env has no terms buffer attached (use_terms_buffer)")
-        key = (id(bufs), None if quota is None else quota.data_ptr(), terms.data_ptr())
-        hit = self._steps.get(key)
-        if hit is None or hit[0] is not bufs:
-            t = bufs.env_done
-            if t.dtype != torch.uint8 or tuple(t.shape) != (self.E,) or not t.is_contiguous():
-                raise ValueError(f"env_done {tuple(t.shape)} {t.dtype}: expected ({self.E},) uint8")
-            if quota is not None and (quota.dtype != torch.int32 or tuple(quota.shape) != (self.E,)
-                                      or not quota.is_contiguous()):
-                raise ValueError("quota: int32 [E]")
-            p = _native.TermsStep()
-            p.terms, p.env_done, p.E, p.N = terms.data_ptr(), t.data_ptr(), self.E, self.N
-            p.quota = None if quota is None else quota.data_ptr()
-            if len(self._steps) > 64:
-                self._steps.clear()
-            hit = self._steps[key] = (bufs, ctypes.byref(p), quota, p, terms)
-        rc = self._accumulate(self._st_ref, hit[1], torch.cuda.current_stream().cuda_stream)
+        args = self._args(bufs, quota, (terms.data_ptr(),), (terms,))
+        rc = self._accumulate(self._st_ref, args, torch.cuda.current_stream().cuda_stream)
         if rc != 0:
-            _chk(rc, "aac_terms_accumulate")
+            check(rc, "aac_terms_accumulate", self.ERROR)
 
-    def raw(self, clear=False):
-        """The folded totals record as int64 [FIELDS] (view as float64 for the sums); synchronises."""
-        _chk(_native.lib().aac_terms_reduce(self._st_ref, self.E, ctypes.c_void_p(self.totals.data_ptr()),
-                                            int(bool(clear)), _stream()), "aac_terms_reduce")
-        return self.totals.cpu().numpy()
+    def _build(self, bufs, quota, terms_ptr):
+        t = bufs.env_done
+        if t.dtype != torch.uint8 or tuple(t.shape) != (self.E,) or not t.is_contiguous():
+            raise ValueError(f"env_done {tuple(t.shape)} {t.dtype}: expected ({self.E},) uint8")
+        p = _native.TermsStep()
+        p.quota = self._quota_ptr(quota)
+        p.terms, p.env_done, p.E, p.N = terms_ptr, t.data_ptr(), self.E, self.N
+        return p
+
+    raw = SlotTally._reduce
 
     def read(self, clear=False):
         """``{"episodes": n, "return_mean": sum of the slot means, "terms": {name: {"mean", "std", "min",

@@ -72,14 +72,7 @@ class CheckpointMixin:
         extra = {f"cur.{k}": v for k, v in vars(self.cur).items() if torch.is_tensor(v)}
         if getattr(self, "gru", False):
             extra["h"] = self.h
-        if getattr(self, "stats", None) is not None:
-            extra.update({f"stats.{k}": v for k, v in self.stats.tensors().items()})
-        if getattr(self, "monitor", None) is not None:
-            extra.update({f"monitor.{k}": v for k, v in self.monitor.tensors().items()})
-        if getattr(self, "visits", None) is not None:
-            extra.update({f"visits.{k}": v for k, v in self.visits.tensors().items()})
-        if getattr(self, "sorties", None) is not None:
-            extra.update({f"sorties.{k}": v for k, v in self.sorties.tensors().items()})
+        extra.update(self.tally.checkpoint_extra())
         return dict(learner=self.model, replay=self.replay, env=self.env, extra=extra)
 
     def save_checkpoint(self, path):
@@ -97,39 +90,40 @@ class CheckpointMixin:
                 self._sg, self._sg2 = {}, {}
             self._pos_dirty = True
 
-    def _init_stats(self, stats):
-        self.stats = None
+    def _init_tallies(self, A, dtype, stats, monitor, terms, visits, sorties=False):
+        """The loop's diagnostics, ``self.tally`` in launch order (each attribute None when off):
+        ``stats``: ``self.stats``.  ``monitor``: True (a ring of 64 updates) or a ring length, of A columns
+        of ``dtype``: ``self.monitor``, attached to the model before its first update plan.  ``terms``:
+        ``self.ledger``; the env's step launches take their terms form from here on (no graph exists yet).
+        ``visits``: True (50 x 50 position bins, 20 x 20 action bins, the model's default noise period) or
+        a dict of ``VisitMap`` keywords (grid, act_bins, explore_until): ``self.visits``.  ``sorties``: True
+        or a dict of ``SortieStats`` keywords (log, reach_margin): ``self.sorties``; UAM only, the ATT / GRU
+        ``Trainer`` resets inside its fused step launch."""
+        from .tally import ACT, STEP, Tallies
+        uam = isinstance(self, UamTrainer)
+        self.tally = Tallies()
+        self.stats = self.monitor = self.ledger = self.visits = self.sorties = None
         if stats:
             from .stats import EpisodeStats
-            self.stats = EpisodeStats.for_env(self.env)
-
-    def _init_visits(self, visits):
-        """``visits``: False / None (off), True (50 x 50 position bins, 20 x 20 action bins, the model's
-        default noise period) or a dict of ``VisitMap`` keywords (grid, act_bins, explore_until)."""
-        self.visits = None
-        if visits:
-            from .visits import VisitMap
-            kw = dict(visits) if isinstance(visits, dict) else {}
-            self.visits = VisitMap(self.env, **kw)
-
-    def _init_sorties(self, sorties):
-        """``sorties``: False / None (off), True or a dict of ``SortieStats`` keywords (log, reach_margin).
-        UAM only: the ATT / GRU ``Trainer`` resets inside its fused step launch."""
-        self.sorties = None
-        if sorties:
-            from .sorties import SortieStats
-            kw = dict(sorties) if isinstance(sorties, dict) else {}
-            self.sorties = SortieStats.for_uam(self.env, **kw)
-
-    def _init_monitor(self, monitor, A, dtype):
-        """``monitor``: False / None (off), True (a ring of 64 updates) or a ring length.  Built and
-        attached to the model before its first update plan."""
-        self.monitor = None
+            self.stats = self.tally.add(EpisodeStats.for_env(self.env), STEP, "stats", "")
         if monitor:
             from .monitor import LearnerMonitor
             ring = 64 if monitor is True else int(monitor)
-            self.monitor = LearnerMonitor(A, ring=ring, dtype=dtype, device=self.model.device)
+            self.monitor = self.tally.add(LearnerMonitor(A, ring=ring, dtype=dtype, device=self.model.device),
+                                          ckpt="monitor")
             self.model.attach_monitor(self.monitor)
+        if terms:
+            from .terms import RewardLedger
+            self.ledger = self.tally.add((RewardLedger.for_uam if uam else RewardLedger.for_env)(self.env), STEP,
+                                         key="terms")
+        if visits:
+            from .visits import VisitMap
+            kw = dict(visits) if isinstance(visits, dict) else {}
+            self.visits = self.tally.add(VisitMap(self.env, **kw), ACT, "visits", "visits")
+        if sorties:
+            from .sorties import SortieStats
+            kw = dict(sorties) if isinstance(sorties, dict) else {}
+            self.sorties = self.tally.add(SortieStats.for_uam(self.env, **kw), STEP, "sorties", "sorties")
 
     def finish(self):
         """End of a run: checks that no launch overflowed the env's exact threshold fix-up list
@@ -141,24 +135,38 @@ class CheckpointMixin:
         Synchronises."""
         if hasattr(self.env, "check_band_capacity"):
             self.env.check_band_capacity()
-        if getattr(self, "monitor", None) is not None:
+        if self.monitor is not None:
             self.monitor.check()
-        out = self.stats.read() if self.stats is not None else None
-        if getattr(self, "ledger", None) is not None:      # with a ledger: the statistics plus its report
-            out = dict(out or {}, terms=self.ledger.read())
+        out = self.tally.report(None, ("", "terms"))       # with a ledger: the statistics plus its report
         if getattr(self.model, "clip", None) is not None:  # with gradient clipping: the model's clip record
             out = dict(out or {}, clip=self.model.clip_record())
-        if getattr(self, "visits", None) is not None:      # with exploration maps: their arrays
-            out = dict(out or {}, visits=self.visits.read())
-        if getattr(self, "sorties", None) is not None:     # with sortie statistics: their report
-            out = dict(out or {}, sorties=self.sorties.read())
-        return out
+        return self.tally.report(out, ("visits", "sorties"))
 
     def terms(self):
         """The reward ledger's report (``terms.RewardLedger.read()``; None without ``terms=True``).
         Synchronises."""
-        led = getattr(self, "ledger", None)
-        return led.read() if led is not None else None
+        out = self.tally.report(None, ("terms",))
+        return out and out["terms"]
+
+    def hooked(self):
+        return bool(self.pre_step_hooks or self.post_step_hooks)
+
+    def step_graph_pair(self, steps=2):
+        """``steps`` (even) training steps as ONE graph replay (the buffer parities in sequence): the
+        GPU idles at each graph launch boundary (~6-9 us between the end of one replay and the first
+        kernel of the next), so k steps per replay cut those gaps k-fold.  The same launches and
+        results as ``steps`` ``step_graph`` calls."""
+        assert steps >= 2 and steps % 2 == 0
+        p = 0 if self.cur is self.bufs[0] else 1
+        self._graphs_current()
+        if not getattr(self, "_sg2", None):
+            self._sg2 = {}
+        if (p, steps) not in self._sg2:
+            self._sg2[(p, steps)] = self._capture_step(p, steps=steps)
+        self._advance_mirror(0)
+        with trace.range("step_graph_pair"):
+            self._sg2[(p, steps)][0].replay()
+        self._advance_mirror(steps)
 
 
 class Trainer(CheckpointMixin):
@@ -247,13 +255,7 @@ class Trainer(CheckpointMixin):
         # the auto-reset of an unfused tail and before the update).  A step with hooks runs eagerly
         # (no whole-step graph).  tests/oracle_diff.py hooks the C oracle in this way.
         self.pre_step_hooks, self.post_step_hooks = [], []
-        self._init_stats(stats)
-        self._init_monitor(monitor, N, torch.float32)
-        self.ledger = None
-        if terms:       # the env's step launches take their terms form from here on (no graph exists yet)
-            from .terms import RewardLedger
-            self.ledger = RewardLedger.for_env(self.env)
-        self._init_visits(visits)
+        self._init_tallies(N, torch.float32, stats, monitor, terms, visits)
 
     def graph_ok(self):
         """Whole-step graphs: the fused env tail, one rank, the fused learner (ATT: AAC_STEP_GRAPH; the
@@ -264,9 +266,6 @@ class Trainer(CheckpointMixin):
         return (STEP_GRAPH and self.fused_tail and self.model.world == 1 and self.model.fused
                 and not NO_GRAPH and len(self.replay) > self.B and not self.hooked())
 
-    def hooked(self):
-        return bool(self.pre_step_hooks or self.post_step_hooks)
-
     def _step_body(self, p, side=None):
         """The launches of one training step whose current buffers are bufs[p] (act + env step tail +
         update_myown), for capture: the ring position is read from / advanced in pos_dev[p] /
@@ -276,26 +275,18 @@ class Trainer(CheckpointMixin):
             # the hidden-state pair flips with the buffer pair: parity p reads hp[p ^ hoff]
             hin, hout = self.hp[p ^ self._hoff], self.hp[1 - (p ^ self._hoff)]
             act, hn = self.model.act(c.own, c.radar, hin, self.episode, noisy=True, h_out=hout)
-            if self.visits is not None:
-                self.visits.accumulate(act)
+            self.tally.after_act(act)
             srcs = [c.own, c.radar, c.nei, act, n.reward, n.done, n.own, n.radar, n.nei, hin, hn]
             self.env.step_tail(act, out=n, replay=self.replay, srcs=srcs, zero_rows=hn,
                                pos_io=(self.pos_dev[p], self.pos_dev[1 - p]))
-            if self.stats is not None:
-                self.stats.accumulate(n)
-            if self.ledger is not None:
-                self.ledger.accumulate(n)
+            self.tally.after_step(n)
             self.model._plan(self.B).run()
             return
         act = self.model.act(c.own, c.radar, c.nei, self.episode, noisy=True)
-        if self.visits is not None:
-            self.visits.accumulate(act)
+        self.tally.after_act(act)
         srcs = [c.own, c.radar, c.nei, act, n.reward, n.done, n.own, n.radar, n.nei]
         self.env.step_tail(act, out=n, replay=self.replay, srcs=srcs, pos_io=(self.pos_dev[p], self.pos_dev[1 - p]))
-        if self.stats is not None:
-            self.stats.accumulate(n)
-        if self.ledger is not None:
-            self.ledger.accumulate(n)
+        self.tally.after_step(n)
         self.model._fused_plan(self.B).run_streams(side)
 
     def _capture_step(self, p, steps=1):
@@ -358,23 +349,6 @@ class Trainer(CheckpointMixin):
             self._sg[p][0].replay()
         self._advance_mirror(1)
 
-    def step_graph_pair(self, steps=2):
-        """``steps`` (even) training steps as ONE graph replay (the buffer parities in sequence): the
-        GPU idles at each graph launch boundary (~6-9 us between the end of one replay and the first
-        kernel of the next), so k steps per replay cut those gaps k-fold.  The same launches and
-        results as ``steps`` ``step_graph`` calls."""
-        assert steps >= 2 and steps % 2 == 0
-        p = 0 if self.cur is self.bufs[0] else 1
-        self._graphs_current()
-        if not getattr(self, "_sg2", None):
-            self._sg2 = {}
-        if (p, steps) not in self._sg2:
-            self._sg2[(p, steps)] = self._capture_step(p, steps=steps)
-        self._advance_mirror(0)
-        with trace.range("step_graph_pair"):
-            self._sg2[(p, steps)][0].replay()
-        self._advance_mirror(steps)
-
     def env_episode_view(self):
         # the env's own per-env episode counter (advanced by each auto-reset; 1 after the first)
         # drives the noise schedule (env e's own episode index, ATT/maddpg:476-477)
@@ -391,8 +365,7 @@ class Trainer(CheckpointMixin):
                 act, hn = self.model.act(c.own, c.radar, self.h, self.episode, noisy=True, h_out=hn_buf)
             else:
                 act = self.model.act(c.own, c.radar, c.nei, self.episode, noisy=True)
-            if self.visits is not None:      # the positions these actions are taken from
-                self.visits.accumulate(act)
+            self.tally.after_act(act)      # the positions these actions are taken from
         if time_env:
             ev0 = torch.cuda.Event(enable_timing=True)
             ev1 = torch.cuda.Event(enable_timing=True)
@@ -408,10 +381,7 @@ class Trainer(CheckpointMixin):
                 else:
                     srcs = [c.own, c.radar, c.nei, act, n.reward, n.done, n.own, n.radar, n.nei]
                     self.env.step_tail(act, out=n, replay=self.replay, srcs=srcs)
-                if self.stats is not None:
-                    self.stats.accumulate(n)
-                if self.ledger is not None:
-                    self.ledger.accumulate(n)
+                self.tally.after_step(n)
             if time_env:
                 ev1.record()
                 self.env_events.append((ev0, ev1))
@@ -424,10 +394,7 @@ class Trainer(CheckpointMixin):
             return
         with trace.range("env_step"):
             self.env.step(act, out=n)
-            if self.stats is not None:
-                self.stats.accumulate(n)
-            if self.ledger is not None:
-                self.ledger.accumulate(n)
+            self.tally.after_step(n)
         if time_env:
             ev1.record()
             self.env_events.append((ev0, ev1))
@@ -530,14 +497,7 @@ class UamTrainer(CheckpointMixin):
         self._sg, self._sg2 = {}, {}                  # parity -> captured whole-step graph (1 / 2 steps)
         self.pos_dev = torch.zeros(2, dtype=torch.int64, device="cuda")   # ring position ping-pong
         self._pos_dirty = True
-        self._init_stats(stats)
-        self._init_monitor(monitor, 1, torch.float64)
-        self.ledger = None
-        if terms:       # the env's step launches take their terms form from here on (no graph exists yet)
-            from .terms import RewardLedger
-            self.ledger = RewardLedger.for_uam(self.env)
-        self._init_visits(visits)
-        self._init_sorties(sorties)
+        self._init_tallies(1, torch.float64, stats, monitor, terms, visits, sorties)
 
     def graph_ok(self):
         """Whole-step graphs: one rank, the fused learner, the replay past one batch, no hooks."""
@@ -545,24 +505,15 @@ class UamTrainer(CheckpointMixin):
         return (UAM_STEP_GRAPH and m.world == 1 and m.fused_learner and not NO_GRAPH
                 and len(self.replay) > self.B and not self.hooked())
 
-    def hooked(self):
-        return bool(self.pre_step_hooks or self.post_step_hooks)
-
     def _step_body(self, p, side):
         """The launches of ``step(update=True)`` from buffer parity p, for capture: the push reads /
         advances the ring position in pos_dev[p] / pos_dev[1 - p] (aac_uam_push_io); the update is the
         fused learner's raw launches."""
         c, n = self.bufs[p], self.bufs[1 - p]
         act = self.model.act(c.own, c.radar, self.episode, noisy=True)
-        if self.visits is not None:
-            self.visits.accumulate(act)
+        self.tally.after_act(act)
         self.env.step(act, out=n)
-        if self.stats is not None:
-            self.stats.accumulate(n)
-        if self.ledger is not None:
-            self.ledger.accumulate(n)
-        if self.sorties is not None:
-            self.sorties.accumulate(n)
+        self.tally.after_step(n)
         self.replay.push_batch(c.own, c.radar, act, n.reward, n.done, n.own, n.radar,
                                pos_io=(self.pos_dev[p], self.pos_dev[1 - p]))
         fu = self.model.fused(self.B, self.replay)
@@ -620,18 +571,6 @@ class UamTrainer(CheckpointMixin):
             self._sg[p][0].replay()
         self._advance_mirror(1)
 
-    def step_graph_pair(self, steps=2):
-        """``steps`` (even) training steps as one graph replay (the buffer parities in sequence)."""
-        assert steps >= 2 and steps % 2 == 0
-        p = 0 if self.cur is self.bufs[0] else 1
-        self._graphs_current()
-        if (p, steps) not in self._sg2:
-            self._sg2[(p, steps)] = self._capture_step(p, steps=steps)
-        self._advance_mirror(0)
-        with trace.range("step_graph_pair"):
-            self._sg2[(p, steps)][0].replay()
-        self._advance_mirror(steps)
-
     def step(self, update=True, time_env=False):
         self._pos_dirty = True
         c, n = self.cur, self.nxt
@@ -639,19 +578,13 @@ class UamTrainer(CheckpointMixin):
             f(self)
         with trace.range("act"):
             act = self.model.act(c.own, c.radar, self.episode, noisy=True)
-            if self.visits is not None:
-                self.visits.accumulate(act)
+            self.tally.after_act(act)
         if time_env:
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ev0.record()
         with trace.range("env_step"):
             self.env.step(act, out=n)
-            if self.stats is not None:
-                self.stats.accumulate(n)
-            if self.ledger is not None:
-                self.ledger.accumulate(n)
-            if self.sorties is not None:
-                self.sorties.accumulate(n)
+            self.tally.after_step(n)
         if time_env:
             ev1.record()
             self.env_events.append((ev0, ev1))

@@ -6,7 +6,7 @@ timed loops, in one process, alternating, on ONE trainer.
   config 5   UamTrainer(8192, 16, B = 512, replay 2^20), host-launched ``step``
 
 One trainer per config is built with ``stats=True``, pre-filled and warmed up.  "Off" is the same
-trainer with ``trainer.stats = None`` and whole-step graphs of its own (captured without the tally
+trainer with the statistics left out of ``trainer.tally`` and whole-step graphs of its own (captured without the tally
 node): both variants run on the same env, buffers, replay and learner.  (Two trainer instances in one
 process differ by more than the tally: with the launch replaced by a no-op, the instance built second
 still ran config 5 43 us per step slower than the first.)  Then ROUNDS rounds of STEPS steps each are
@@ -42,13 +42,14 @@ class Variants:
 
     def __init__(self, tr):
         self.tr, self.stats, self.on = tr, tr.stats, True
+        self.tally = {True: tr.tally, False: tr.tally.without(tr.stats)}
         self.graphs = {True: ({}, {}), False: ({}, {})}
 
     def select(self, on):
         tr = self.tr
         self.graphs[self.on] = (tr._sg, getattr(tr, "_sg2", None) or {})
         tr._sg, tr._sg2 = self.graphs[on]
-        tr.stats = self.stats if on else None
+        tr.stats, tr.tally = self.stats if on else None, self.tally[on]
         self.on = on
 
 

@@ -42,6 +42,7 @@ class Variants:
     def __init__(self, tr):
         self.tr, self.cur = tr, "on"
         self.ledger, self.buf = tr.ledger, tr.env.terms
+        self.tally = {"on": tr.tally, "off": tr.tally.without(tr.ledger)}
         if not hasattr(tr, "_sg2"):
             tr._sg2 = {}
         self.kept = {}
@@ -56,6 +57,7 @@ class Variants:
         else:
             tr.env.use_terms_buffer(detach=True)
             tr.ledger = None
+        tr.tally = self.tally[name]
         self.cur = name
 
 

@@ -6,7 +6,7 @@ accumulate launch on its own beside the episode statistics' accumulate launch.
   config 5   UamTrainer(8192, 16, B = 512, replay 2^20), host-launched ``step``
 
 One trainer per config is built with ``visits=True, stats=True``, pre-filled and warmed up.  "Off" is
-the same trainer with ``trainer.visits = None`` and whole-step graphs of its own (captured without the
+the same trainer with the maps left out of ``trainer.tally`` and whole-step graphs of its own (captured without the
 launch): both variants run on the same env, buffers, replay and learner.  ROUNDS rounds of STEPS steps
 are timed for each variant in turn (off, on, off, on, ...), a host clock around work that ends in a
 device synchronise.  Printed per config: every round's ms per step, the medians, the difference
@@ -47,13 +47,14 @@ class Variants:
 
     def __init__(self, tr):
         self.tr, self.visits, self.on = tr, tr.visits, True
+        self.tally = {True: tr.tally, False: tr.tally.without(tr.visits)}
         self.graphs = {True: ({}, {}), False: ({}, {})}
 
     def select(self, on):
         tr = self.tr
         self.graphs[self.on] = (tr._sg, getattr(tr, "_sg2", None) or {})
         tr._sg, tr._sg2 = self.graphs[on]
-        tr.visits = self.visits if on else None
+        tr.visits, tr.tally = self.visits if on else None, self.tally[on]
         self.on = on
 
 
