@@ -108,7 +108,9 @@ int aac_uam_sorties(aac_uam *env, const aac_sortie_state *state, const aac_sorti
 
 /* Host: draw n episodes with the reference's rules (UAM/env:575-747, UAM/util:165-237): cloud
  * choices, starts in the two start zones re-drawn until > 3 pB from earlier starts, ends uniform
- * over the no-spawn-subtracted regions on the start's side of the runway. */
+ * over the no-spawn-subtracted regions on the start's side of the runway.  2 <= N <= 40: the two
+ * 2 m x 10 m zones cannot hold more than 40 starts 3 pB apart (disc packing), and a request past that
+ * returns AAC_E_INVALID.  (An aircraft that finds no free start in 100000 draws keeps its last one.) */
 int aac_uam_bank_build(int32_t n, int32_t N, uint64_t seed, double *start, double *goal, int32_t *clouds);
 
 /* Batched choose_action of the UAM learner (UAM/maddpg:597-676) on the fp64 matrix cores:

@@ -1784,8 +1784,16 @@ int aac_uam_probe(aac_uam *h, const double *pos, const double *clouds, const int
     return AAC_OK;
 }
 
+constexpr int BANK_MAX_N = 40;     // see aac_uam_bank_build
+
 int aac_uam_bank_build(int32_t n, int32_t N, uint64_t seed, double *start, double *goal, int32_t *clouds) {
     if (n <= 0 || N < 2 || N > MAXA || !start || !goal || !clouds) return ufail(AAC_E_INVALID, "bad bank request");
+    // Starts pairwise > 1.5 m apart are centres of disjoint discs of radius 0.75 m inside a zone grown by
+    // 0.75 m (3.5 m x 11.5 m); at the densest packing (pi / sqrt(12)) that is 20 discs per zone, 40 in all.
+    // Past that every episode would spend 100000 draws on each aircraft it cannot place and keep an
+    // overlapping start: refused.
+    if (N > BANK_MAX_N)
+        return ufail(AAC_E_INVALID, "bank build: the two start zones cannot hold more than 40 starts 3 pB apart");
     const double b[4] = {0.0, 40.0, 0.0, 40.0};
     const double zones[2][4] = {{15, 17, 15, 25}, {23, 25, 15, 25}};
     const double sep = 0.5 * 3;

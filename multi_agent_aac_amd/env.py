@@ -203,6 +203,8 @@ class BatchedEnv:
         o = out.c_struct()
         _native.check(_native.lib().aac_env_step_tail(self._h, _ptr(a), ctypes.byref(o), ctypes.byref(t), _stream()),
                       "aac_env_step_tail")
+        if replay is not None:
+            replay.tail_pushed(self.E)      # only now: a refused call launched nothing, the ring did not advance
         return out
 
     def set_od_bank(self, bank, seed=0):

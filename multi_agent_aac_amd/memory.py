@@ -78,8 +78,9 @@ class DeviceReplay:
 
     def tail_push(self, srcs, E):
         """The push of ``push_batch(*srcs)`` as the replay part of a fused env step tail
-        (``BatchedEnv.step_tail``, aac_env_step_tail): returns the aac_step_tail fields and advances
-        the host mirror of the ring position (the launch advances ``meta``)."""
+        (``BatchedEnv.step_tail``, aac_env_step_tail): returns the aac_step_tail fields.  The caller
+        advances the host mirror of the ring position with ``tail_pushed`` once the launch is accepted
+        (the launch advances ``meta``; a refused call launches nothing)."""
         if self.H:
             assert len(srcs) == 11, "this replay stores hidden states"
         else:
@@ -91,9 +92,12 @@ class DeviceReplay:
                  size=self.size, meta=self.meta.data_ptr(), n_fields=n,
                  srcs=(ctypes.c_void_p * n)(*[t.data_ptr() for t in srcs]),
                  widths=(ctypes.c_int32 * n)(*self.widths[:n]), dtypes=(ctypes.c_int32 * n)(*self.dtypes[:n]))
+        return d
+
+    def tail_pushed(self, E):
+        """The fused tail pushed E rows: advance the host mirror."""
         self.pos = (self.pos + E) % self.capacity
         self.size = min(self.size + E, self.capacity)
-        return d
 
     def check_sample(self, B):
         """random.sample semantics need at least B stored rows (the reference guards with

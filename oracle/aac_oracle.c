@@ -601,7 +601,10 @@ void oc_step(const oc_cfg *c, oc_state *s, const float *act, oc_out *o) {
     const int N = c->N, E = c->E;
     const double *b = c->bound;
     const double pb = 2.5, vmax = c->vmax, dt = 0.5;
-    double rew[64], rmin[64];
+    /* per-agent scratch sized by N (any N the ABI accepts, 2..256): rew | rmin | dist */
+    double *rew = malloc(sizeof(double) * 3 * (size_t)(N > 0 ? N : 1));
+    if (!rew) abort();
+    double *rmin = rew + N, *dist = rmin + N;
     for (int e = 0; e < E; ++e) {
         /* a1 kinematics */
         for (int i = 0; i < N; ++i) {
@@ -632,7 +635,7 @@ void oc_step(const oc_cfg *c, oc_state *s, const float *act, oc_out *o) {
             size_t ai = (size_t)e * N + i;
             double px = s->pos[2 * ai], py = s->pos[2 * ai + 1];
             int ncoll = 0, last_coll = -1, nearest = -1;
-            double shortest = INFINITY, dist[64];
+            double shortest = INFINITY;
             int nd = 0;
             for (int j = 0; j < N; ++j) {
                 if (j == i) continue;
@@ -702,6 +705,7 @@ void oc_step(const oc_cfg *c, oc_state *s, const float *act, oc_out *o) {
         s->step[e] += 1;
         o->env_done[e] = (uint8_t)((c->episode_length < s->step[e]) || any_done || all_goal || all_reach);
     }
+    free(rew);
 }
 
 /* reset selected envs to the given OD and write their observation (env:199-405) */

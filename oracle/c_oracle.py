@@ -14,6 +14,7 @@ from .consts import BOUND, EPISODE_LENGTH, N_RAYS
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "_build", "libaac_oracle.so")
+N_MAX = 256        # aac_env_create: 2 <= N <= 256; oc_step sizes its per-agent arrays by N
 
 
 def build():
@@ -73,6 +74,8 @@ class BatchedOracle:
                  bound=BOUND, with_tdcpa=False, team_reward=True, variant="att"):
         """variant "att" (one_model_att) or "wgru" (randomOD_Wgru_radar, config 4: obstacle radar,
         6-wide own rows, per-agent WGRU ss_reward, max_spd 10, episode_length 150 by default)."""
+        if not 2 <= N <= N_MAX:
+            raise ValueError(f"BatchedOracle: N = {N} outside 2..{N_MAX} (the agent counts aac_env_create accepts)")
         self.E, self.N, self.W = E, N, W
         self.K = N - 1
         self.variant = {"att": 0, "wgru": 1}[variant]

@@ -78,11 +78,12 @@ def test_uam_reset_matches_oracle(native_lib, N):
         assert s["cloud_tgt"][e] == 1 and s["step"][e] == 0
 
 
-def _stepped_pair(N, E, seed, steps, act_scale=1.0):
+def _stepped_pair(N, E, seed, steps, act_scale=1.0, episodes=None):
     """Run the device free; after each step check every env against the oracle started from the
-    device's own pre-step state.  Returns the per-step mask arrays."""
+    device's own pre-step state.  Returns the per-step mask arrays.  ``episodes`` (start, goal,
+    clouds) replaces the reference's draw."""
     from multi_agent_aac_amd import uam
-    st, go, cl = _episodes(E, N, seed)
+    st, go, cl = episodes if episodes is not None else _episodes(E, N, seed)
     env = uam.BatchedUAM(E, N, p3=True, tdcpa=True)
     env.reset(st, go, cl)
     rng = np.random.default_rng(seed)
