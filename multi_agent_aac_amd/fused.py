@@ -72,6 +72,28 @@ class DaobArgs(ctypes.Structure):
 
 GEMM_MAX = 16
 HEAD_MAX = 1
+
+# Agent counts N of the ATT learner (K = N - 1 neighbours, D0 = 6 + 4 K, critic rows of Din = D0 + 2).
+# The attention entry points take 1 <= K <= ATTN_K_MAX; aac_attn_enc_fwd, which every fused launch list
+# (FusedUpdate, ActorInfer, the TD-target chain) goes through, takes K <= ENC_K_MAX and own / critic
+# rows of at most ENC_DMAX floats.  The native checks hold the same numbers (csrc/aac_fused.hip,
+# csrc/aac_learn.hip).
+ATTN_K_MAX = 32
+ENC_K_MAX, ENC_DMAX = 8, 40
+N_MIN, N_MAX = 2, ATTN_K_MAX + 1                                        # fused=False: 2..33
+FUSED_N_MIN = N_MIN
+FUSED_N_MAX = min(ENC_K_MAX + 1, (ENC_DMAX - 8) // 4 + 1)               # K <= 8 and 8 + 4 K <= 40: 9
+
+
+def check_agents(N, fused):
+    """Refuse an agent count no launch of the chosen learner accepts (ValueError)."""
+    if not N_MIN <= N <= N_MAX:
+        raise ValueError(f"n_agents = {N}: the ATT learner supports {N_MIN}..{N_MAX} agents "
+                         f"(the attention kernels hold 1 <= K = N - 1 <= {ATTN_K_MAX} neighbours)")
+    if fused and not FUSED_N_MIN <= N <= FUSED_N_MAX:
+        raise ValueError(f"n_agents = {N}: the fused learner (fused=True) supports {FUSED_N_MIN}..{FUSED_N_MAX} agents "
+                         f"(aac_attn_enc_fwd: K <= {ENC_K_MAX}, rows of at most {ENC_DMAX} floats); "
+                         f"fused=False runs up to {N_MAX}")
 _L = None
 
 

@@ -23,6 +23,7 @@ import torch.nn.functional as F
 from . import graphs as _graphs
 from . import clip as _clip
 from . import fused, ops, parallel, trace
+from .fused import check_agents as _check_agents
 from .memory import DeviceReplay, ReplayMemory
 from .networks import ActorNetwork_ATT_TwoPortion, CriticCombine, FlatParams
 
@@ -72,6 +73,7 @@ class MADDPG:
         if self.device.type == "cuda" and self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.n_agents = N = int(n_agents)
+        _check_agents(N, self.fused)        # before anything is built: an unsupported N would fail at a launch
         self.n_actions = int(dim_act)
         self.D0 = 6 + 4 * (N - 1)
         if actor_dim[0] != self.D0:

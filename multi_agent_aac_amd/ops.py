@@ -93,10 +93,13 @@ def masked_attention(q, kv, nei):
 _tickets = {}
 
 
-def _ticket_buf(dev):
+def _ticket_buf(dev, n=64):
+    """At least ``n`` zeroed tickets (aac_act_bgrad takes one per block of 64 columns and leaves it
+    zeroed); grown when a wider layer comes: the critic's stacked encoders are 128 N columns, 66 blocks
+    at N = 33."""
     t = _tickets.get(dev)
-    if t is None:
-        t = _tickets[dev] = torch.zeros(64, dtype=torch.int32, device=dev)   # kernel keeps it zeroed
+    if t is None or t.numel() < n:
+        t = _tickets[dev] = torch.zeros(max(64, n), dtype=torch.int32, device=dev)   # kernel keeps it zeroed
     return t
 
 
@@ -106,7 +109,7 @@ def act_bgrad(gy, y, gm, db, act):
     ws = tk = None
     if db is not None:
         ws = torch.empty(((M + 31) // 32) * O, dtype=torch.float32, device=gy.device)
-        tk = _ticket_buf(gy.device)
+        tk = _ticket_buf(gy.device, (O + 63) // 64)
     _chk(lib().aac_act_bgrad(_p(gy), gy.stride(0), _p(y), y.stride(0) if y is not None else 0, _p(gm),
                              gm.stride(0) if gm is not None else 0, _p(db), M, O, act, _p(ws), _p(tk), _s()),
          "aac_act_bgrad")

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from oracle import learner_ref
+from tests import attn_cases
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -338,7 +339,7 @@ def test_fused_equals_autograd_learner(native_lib):
         np.testing.assert_allclose(a.cpu(), b.cpu(), atol=1e-4, rtol=1e-5)
 
 
-@pytest.mark.parametrize("K", [1, 4, 7, 15])
+@pytest.mark.parametrize("K", attn_cases.K_BLOCK)      # 1, 4, 7, 15 and the instance edges 5, 8, 9, 16, 17, 32
 def test_attn_block_matches_reference_attention(native_lib, K):
     """Fused inference attention (x_j on the fly, Wqk = Wk^T Wq, v_att = Wv sum a_j x_j) against
     the reference's k / v projections and masked softmax (ATT/nets:186-210), fp64."""
@@ -349,6 +350,7 @@ def test_attn_block_matches_reference_attention(native_lib, K):
     nei = torch.randn(R, K, 6, device=DEV)
     nei[::5, 0] = 0.0                          # masked neighbours
     nei[3] = 0.0                               # an all-masked row
+    attn_cases.plant_edge_rows(nei, at=10)     # all masked, only slot K - 1, only slot 0, every slot valid
     Wn, bn = torch.randn(64, 6, device=DEV) * 0.4, torch.randn(64, device=DEV) * 0.1
     Wq, Wk, Wv = (torch.randn(64, 64, device=DEV) * 0.125 for _ in range(3))
     kv = torch.cat([Wk, Wv], 0).contiguous()
@@ -377,18 +379,33 @@ def test_fused_act_matches_ref_actor(native_lib, monkeypatch, ws, E):
     at config 2's size (E = 1024 envs x N = 5 agents; E = 77: a ragged last row block) against
     oracle/learner_ref.RefActor, the CPU restatement of ActorNetwork_ATT_TwoPortion (ATT/nets:177-213),
     loaded with the same reference state_dict."""
+    _fused_act_case(monkeypatch, ws, E, 5)
+
+
+@pytest.mark.parametrize("ws", [True, False])
+@pytest.mark.parametrize("N", attn_cases.ACT_N)
+def test_fused_act_matches_ref_actor_over_agents(native_lib, monkeypatch, N, ws):
+    """The same over the fused act path's agent range at E = 77: N = 2 (one neighbour), N = 6 (the first
+    on attn_enc_kernel<8, 10>) and N = 9 (K = 8, d_own = 38: its limits), both head forms."""
+    _fused_act_case(monkeypatch, ws, attn_cases.ACT_E, N)
+
+
+def _fused_act_case(monkeypatch, ws, E, N):
     from multi_agent_aac_amd import fused
     from multi_agent_aac_amd.maddpg import MADDPG
     monkeypatch.setattr(fused, "ACT_HEAD_WS", ws)
-    m = MADDPG([22, 18, 6], [22, 18, 6], 2, n_agents=5, device=DEV, seed=3)
-    ref = learner_ref.RefActor([22, 18, 6], 2)
+    D0, K = 6 + 4 * (N - 1), N - 1
+    m = MADDPG([D0, 18, 6], [D0, 18, 6], 2, n_agents=N, device=DEV, seed=3)
+    ref = learner_ref.RefActor([D0, 18, 6], 2)
     ref.load_state_dict({k: v.cpu() for k, v in m.actors.reference_state_dict().items()})
     g = torch.Generator().manual_seed(5)
-    N = 5
-    own, radar = torch.randn(E, N, 22, generator=g), torch.rand(E, N, 18, generator=g) * 15
-    nei = torch.randn(E, N, 4, 6, generator=g)
-    nei[::7, :, 1] = 0.0                         # masked neighbours
-    nei[5, 2] = 0.0                              # an all-masked attention row
+    own, radar = torch.randn(E, N, D0, generator=g), torch.rand(E, N, 18, generator=g) * 15
+    nei = torch.randn(E, N, K, 6, generator=g)
+    nei[::7, :, min(1, K - 1)] = 0.0             # masked neighbours
+    nei[5, min(2, N - 1)] = 0.0                  # an all-masked attention row
+    if N != 5:                                   # (N = 5 keeps the inputs it always had)
+        nei[8, 0, :K - 1] = 0.0                  # only the last slot valid
+        nei[9, 0, 1:] = 0.0                      # only the first
     got = m.act(own.to(DEV), radar.to(DEV), nei.to(DEV), noisy=False).clone()
     with torch.no_grad():
         want = learner_ref.actor_rows(ref, own, radar, nei)
@@ -409,7 +426,7 @@ def test_fused_act_matches_ref_actor(native_lib, monkeypatch, ws, E):
     assert float(noise.abs().max()) > 0.1
 
 
-@pytest.mark.parametrize("K", [1, 4, 7, 12])       # K <= 8: MFMA kernels; 12: per-row kernels
+@pytest.mark.parametrize("K", attn_cases.K_TRAIN)  # K <= 8: MFMA kernels; above: per-row <16> (9, 12, 16), <32> (17, 32)
 def test_attn_train_fwd_bwd_matches_autograd(native_lib, K):
     """Training attention kernels (in-kernel q / k / v projections) against fp64 autograd of the
     reference form (ATT/nets:186-210): v_att, and the gradients into x_j, q and e_o."""
@@ -421,6 +438,7 @@ def test_attn_train_fwd_bwd_matches_autograd(native_lib, K):
     nei = torch.randn(R, K, 6, device=DEV)
     nei[::4, 0] = 0.0
     nei[7] = 0.0
+    attn_cases.plant_edge_rows(nei, at=10)
     Wq, Wk, Wv = (torch.randn(64, 64, device=DEV) * 0.125 for _ in range(3))
     kv = torch.cat([Wk, Wv], 0).contiguous()
     cat = torch.zeros(R, 192, device=DEV)

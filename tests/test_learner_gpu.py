@@ -6,7 +6,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import learner_ref
-from tests import noise_ref
+from tests import attn_cases, noise_ref
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -23,7 +23,7 @@ def _ref_attention(q, k, v, nei):
     return torch.sum(v * am, axis=1)
 
 
-@pytest.mark.parametrize("K", [1, 2, 4, 7, 15])
+@pytest.mark.parametrize("K", attn_cases.K_ATTENTION)       # 1, 2, 4, 7, 15 and the instance edges 5, 8, 9, 16, 17, 32
 def test_attention_fwd_bwd(native_lib, K):
     from multi_agent_aac_amd import ops
     torch.manual_seed(K)
@@ -33,6 +33,7 @@ def test_attention_fwd_bwd(native_lib, K):
     nei = torch.randn(R, K, 6, dtype=torch.float64)
     nei[torch.rand(R, K) < 0.3] = 0.0
     nei[:5] = 0.0                                     # all-masked rows
+    attn_cases.plant_edge_rows(nei, at=10)            # only slot K - 1, only slot 0, every slot valid
     dout = torch.randn(R, 64, dtype=torch.float64)
     qr, kvr = q.clone().requires_grad_(), kv.clone().requires_grad_()
     ref = _ref_attention(qr, kvr[..., :64], kvr[..., 64:], nei)

@@ -53,7 +53,8 @@ BWD_BREAKS = {"cat", "ldcat", "dv", "lddv", "dcat_o", "ldd", "dq", "deo"}
 VARIANTS = ["none", "cat", "ldcat", "q", "qk", "nei", "dv", "lddv", "dcat_o", "ldd", "dq", "deo"]
 
 
-def _attn_train_case(R, K, variant):
+def _attn_train_case(R, K, variant, nei_rows=None):
+    """``nei_rows``: the neighbour rows (R, K, 6) to run with instead of the ones drawn here."""
     from multi_agent_aac_amd import fused
     r = _rnd(R * 100 + K)
     sh = lambda k: 1 if variant == k else 0   # noqa: E731
@@ -63,6 +64,8 @@ def _attn_train_case(R, K, variant):
     nei_d[::4, 0] = 0.0                                   # masked neighbours
     if R > 7:
         nei_d[7] = 0.0                                    # an all-masked row
+    if nei_rows is not None:
+        nei_d = nei_rows.clone()
     Wq_d, Wk_d, Wv_d = (r(64, 64) * 0.125 for _ in range(3))
     dv_d, dcat_d = r(R, 64), r(R, 64)
     # cat: e_o in columns 0..63 (read), v_att into columns 128..191, columns 64..127 stay canary
@@ -148,40 +151,47 @@ def test_attn_block_in_the_arena(native_lib, R, K):
     """aac_attn_block (MFMA for K <= 4 on 16-B rows, per-row otherwise) reading e_o from cat and
     writing v_att into cat's last column block, reference of
     test_attn_block_matches_reference_attention; then with cat moved by one float and with ld 193."""
-    from multi_agent_aac_amd import fused
     for variant in ("none", "cat", "ldcat"):
-        r = _rnd(R * 100 + K + 1)
-        ar = Arena(R * (200 + 8 * K) + 2 * 64 * 64 + 64 * 8 + 2048, torch.float32, DEV, max_ld=200)
-        eo_d = torch.relu(r(R, 64))
-        nei_d = r(R, K, 6)
-        nei_d[::5, 0] = 0.0
-        if R > 3:
-            nei_d[3] = 0.0
-        Wn_d, bn_d = r(64, 6) * 0.4, r(64) * 0.1
-        Wq_d, Wk_d, Wv_d = (r(64, 64) * 0.125 for _ in range(3))
-        cat = ar.take(R, 192, ld=192 + (variant == "ldcat"), misalign=int(variant == "cat"), name="cat", payload=False)
-        eo = cat.sub(0, 0, R, 64, name="cat[:, :64]", data=eo_d)
-        out = cat.sub(0, 128, R, 64, name="cat[:, 128:]")
-        nei = ar.take(R * K, 6, name="nei", data=nei_d.reshape(R * K, 6))
-        Wn, bn = ar.take(64, 6, name="Wn", data=Wn_d), ar.vec(64, name="bn", data=bn_d)
-        wqk = ar.take(64, 64, name="Wqk", data=Wk_d.t() @ Wq_d)
-        Wv = ar.take(64, 64, name="Wv", data=Wv_d)
-        for reg in (cat, nei, Wn, bn, wqk, Wv):
-            ar.inside_mat(reg.ptr, reg.rows, reg.cols, reg.ld, reg.name)
-        fused.attn_block(eo.ptr, cat.ld, nei.ptr, Wn.ptr, bn.ptr, wqk.ptr, Wv.ptr, out.ptr, cat.ld, R, K)
-        torch.cuda.synchronize()
-        d = lambda t: t.double()   # noqa: E731
-        x = torch.relu(d(nei_d) @ d(Wn_d).t() + d(bn_d))
-        qv = d(eo_d) @ d(Wq_d).t()
-        k, v = x @ d(Wk_d).t(), x @ d(Wv_d).t()
-        score = torch.einsum("rkc,rc->rk", k, qv) / 8.0
-        mask = d(nei_d).mean(-1) != 0
-        score[~mask] = float("-inf")
-        a = torch.softmax(score, dim=1)
-        a[~mask] = 0.0
-        a = torch.nan_to_num(a)
-        close(out.get(), torch.einsum("rk,rkc->rc", a, v), 2e-5, 1e-5, f"R {R} K {K} {variant}")
-        ar.check(writable=[out])
+        _attn_block_case(R, K, variant)
+
+
+def _attn_block_case(R, K, variant, nei_rows=None):
+    """One aac_attn_block launch in the arena; variant "cat": cat moved by one float, "ldcat": ld 193."""
+    from multi_agent_aac_amd import fused
+    r = _rnd(R * 100 + K + 1)
+    ar = Arena(R * (200 + 8 * K) + 2 * 64 * 64 + 64 * 8 + 2048, torch.float32, DEV, max_ld=200)
+    eo_d = torch.relu(r(R, 64))
+    nei_d = r(R, K, 6)
+    nei_d[::5, 0] = 0.0
+    if R > 3:
+        nei_d[3] = 0.0
+    if nei_rows is not None:
+        nei_d = nei_rows.clone()
+    Wn_d, bn_d = r(64, 6) * 0.4, r(64) * 0.1
+    Wq_d, Wk_d, Wv_d = (r(64, 64) * 0.125 for _ in range(3))
+    cat = ar.take(R, 192, ld=192 + (variant == "ldcat"), misalign=int(variant == "cat"), name="cat", payload=False)
+    eo = cat.sub(0, 0, R, 64, name="cat[:, :64]", data=eo_d)
+    out = cat.sub(0, 128, R, 64, name="cat[:, 128:]")
+    nei = ar.take(R * K, 6, name="nei", data=nei_d.reshape(R * K, 6))
+    Wn, bn = ar.take(64, 6, name="Wn", data=Wn_d), ar.vec(64, name="bn", data=bn_d)
+    wqk = ar.take(64, 64, name="Wqk", data=Wk_d.t() @ Wq_d)
+    Wv = ar.take(64, 64, name="Wv", data=Wv_d)
+    for reg in (cat, nei, Wn, bn, wqk, Wv):
+        ar.inside_mat(reg.ptr, reg.rows, reg.cols, reg.ld, reg.name)
+    fused.attn_block(eo.ptr, cat.ld, nei.ptr, Wn.ptr, bn.ptr, wqk.ptr, Wv.ptr, out.ptr, cat.ld, R, K)
+    torch.cuda.synchronize()
+    d = lambda t: t.double()   # noqa: E731
+    x = torch.relu(d(nei_d) @ d(Wn_d).t() + d(bn_d))
+    qv = d(eo_d) @ d(Wq_d).t()
+    k, v = x @ d(Wk_d).t(), x @ d(Wv_d).t()
+    score = torch.einsum("rkc,rc->rk", k, qv) / 8.0
+    mask = d(nei_d).mean(-1) != 0
+    score[~mask] = float("-inf")
+    a = torch.softmax(score, dim=1)
+    a[~mask] = 0.0
+    a = torch.nan_to_num(a)
+    close(out.get(), torch.einsum("rk,rkc->rc", a, v), 2e-5, 1e-5, f"R {R} K {K} {variant}")
+    ar.check(writable=[out])
 
 
 # ------------------------------------------------------------------ critic heads
